@@ -22,12 +22,19 @@ overlaps the next step's kernels; after the timed region rank 0 reassembles the
 last step in global cluster order and checks it.  value = the batch's clusters /
 max-over-ranks time.  --scaling weak gives every rank its own 385k-cluster batch.
 
-Extra keys (single GPU): the gap-average consensus on the same batch, the
-north-star run (1M clusters on one MI355X), the configs[3] skewed medoid, bin-mean
-off the headline's shape and the host-inclusive tier 2 (pageable host CSR -> H2D
--> kernels -> D2H) at the headline's size.
+A plain run does only what the headline needs: it generates the batch, runs the
+step once checked (statuses), warms up, times --steps steps, writes the last
+step's results if --dump-outputs DIR is given and prints the line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--clusters C] [--ns-clusters 1000000]
+--full adds everything else: the fused pass compared with the two separate entry
+points before timing, the per-kernel and roofline lines, the CPU baselines and
+(single GPU) the gap-average consensus on the same batch, the north-star run (1M
+clusters on one MI355X), the configs[3] skewed medoid, bin-mean off the headline's
+shape, the host-inclusive tier 2 (pageable host CSR -> H2D -> kernels -> D2H) at
+the headline's size and the MGF-to-MGF tier 3.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--clusters C] [--dump-outputs DIR]
+                    [--full [--ns-clusters 1000000]]
 
 Prints ONE JSON line (rank 0).
 """
@@ -48,6 +55,8 @@ HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec (MI355X_MICROARCH.md: 8.0 TB/s)
 HBM_ACHIEVABLE_GBS = 6290.0  # measured float4 copy ceiling (MI355X_MICROARCH.md chip table)
 I8_DENSE_TOPS = 5000.0       # i8 MFMA dense peak, 2x BF16's ~2.5 PF (MI355X_MICROARCH.md MFMA table)
 FP4_DENSE_TOPS = 10000.0     # FP4 (e2m1) MFMA dense peak, 4x BF16 per clock (same table)
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: all files together
+DUMP_SAMPLE_CLUSTERS = 4096  # --dump-outputs: clusters whose consensus peaks are written
 
 
 def parse():
@@ -59,7 +68,12 @@ def parse():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ns-clusters", type=int, default=1_000_000,
                     help="north-star run size on one GPU (0: skip)")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the fused-vs-separate comparison, per-kernel and roofline lines, CPU baselines "
+                         "and the single-GPU extras (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (rank 0's, world 1) as DIR/<name>.npy")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no single-GPU extras")
     ap.add_argument("--cpu-sample", type=int, default=2000, help="clusters in the CPU-baseline sample (0: skip)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--tier2-chunk-mb", type=int, default=2048, help="tier-2 pipeline chunk (MB of peaks)")
@@ -111,16 +125,18 @@ class HipBackend:
 
         return engine.DeviceBatch.from_device(t)
 
-    def first_step(self, batch):
+    def first_step(self, batch, compare=True):
         """The step once, checked: every cluster resolved by the launch the step makes,
-        and the fused pass (spx_bin_mean_medoid) equal to the two separate entry points,
-        consensus peaks and representatives bit for bit.  Returns (bm, md, separate)."""
+        and (``compare``) the fused pass (spx_bin_mean_medoid) equal to the two separate
+        entry points, consensus peaks and representatives bit for bit.  Returns
+        (bm, md, separate); separate is None without ``compare``."""
         import torch
 
         from specpride_amd import engine
 
-        bm_sep = engine.bin_mean(batch)
-        md_sep = engine.medoid(batch, check=True)
+        if compare:
+            bm_sep = engine.bin_mean(batch)
+            md_sep = engine.medoid(batch, check=True)
         bm, md = engine.bin_mean_medoid(batch, check=True)
         torch.cuda.synchronize()
         C = batch.n_clusters
@@ -128,11 +144,50 @@ class HipBackend:
         rep = md.rep.cpu().numpy()[:C]
         if np.any(st != 0) or np.any(rep < 0):
             raise RuntimeError(f"unexpected statuses: bin-mean {np.unique(st)}, medoid min rep {rep.min()}")
+        if not compare:
+            return bm, md, None
         same = (torch.equal(bm.count[:C], bm_sep.count[:C]) and torch.equal(md.rep[:C], md_sep.rep[:C]) and
                 all(torch.equal(a, b) for a, b in zip(bm.compact()[1:], bm_sep.compact()[1:])))
         if not same:
             raise RuntimeError("spx_bin_mean_medoid differs from spx_bin_mean + spx_medoid")
         return bm, md, (bm_sep, md_sep)
+
+    def dump(self, batch, bm, md, path: str, seed: int) -> dict:
+        """--dump-outputs: the results of the step that last wrote ``bm`` / ``md``, as
+        path/<name>.npy.  The per-cluster arrays whole -- ``rep`` (the representative's
+        global spectrum index), ``count`` (consensus peaks kept), ``status``, ``prec``,
+        ``charge`` -- and the compacted consensus peaks (``out_mz``, ``out_int``, with
+        ``sample_off`` their offsets) of a seeded sample of clusters, ``sample_ids``, cut
+        so that all files stay under DUMP_MAX_BYTES."""
+        import torch
+
+        from specpride_amd.csr import concat_ranges
+
+        torch.cuda.synchronize()
+        C = batch.n_clusters
+        out_off, mz, inten = bm.compact()
+        off = out_off.cpu().numpy()
+        cnt = np.diff(off)
+        arrays = {"rep": md.rep[:C].cpu().numpy().astype(np.float64), "count": cnt.astype(np.float64),
+                  "status": bm.status[:C].cpu().numpy().astype(np.float32),
+                  "prec": bm.prec[:C].cpu().numpy().astype(np.float64),
+                  "charge": bm.charge[:C].cpu().numpy().astype(np.float32)}
+        budget = DUMP_MAX_BYTES - sum(a.nbytes for a in arrays.values()) - (1 << 20)  # 1 MB: headers, offsets
+        if budget < 0:
+            raise RuntimeError(f"--dump-outputs: the per-cluster arrays of {C} clusters alone pass {DUMP_MAX_BYTES} B")
+        order = np.random.default_rng(seed).permutation(C)[:DUMP_SAMPLE_CLUSTERS]
+        take = int(np.searchsorted(np.cumsum(16 * cnt[order] + 16), max(budget, 0), side="right"))
+        ids = np.sort(order[:take])
+        sel = torch.from_numpy(concat_ranges(off[ids], cnt[ids])).to(mz.device)
+        sample_off = np.zeros(len(ids) + 1, np.int64)
+        np.cumsum(cnt[ids], out=sample_off[1:])
+        arrays.update(sample_ids=ids.astype(np.float64), sample_off=sample_off.astype(np.float64),
+                      out_mz=mz[sel].cpu().numpy(), out_int=inten[sel].cpu().numpy())
+        os.makedirs(path, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(path, name + ".npy"), a)
+        return {"dir": path, "clusters": int(C), "sample_clusters": int(len(ids)),
+                "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
     def alloc(self, batch):
         from specpride_amd import engine
@@ -513,8 +568,8 @@ def headline(args, rank, world, local, out, be):
     batch = be.batch(t)
     be.sync()
 
-    # checked once, before timing (HipBackend.first_step: statuses, fused == separate)
-    bm, md, separate = be.first_step(batch)
+    # checked once, before timing (HipBackend.first_step: statuses; --full: fused == separate)
+    bm, md, separate = be.first_step(batch, compare=args.full)
     kept = int(bm.count[:batch.n_clusters].sum().item())
     first = be.first(batch) if strong else None
 
@@ -613,9 +668,14 @@ def headline(args, rank, world, local, out, be):
         out["config"]["assembled_last_step"] = assembled
     out["config"]["step"] = ("spx_bin_mean_medoid: one fused pass per cluster (bin-mean + medoid register bodies "
                              "in one workgroup); the leftover chains only when a register body handed a cluster "
-                             "on (spx_bin_mean_medoid_stage); checked bit-identical to spx_bin_mean + spx_medoid "
-                             "before timing")
-    if be.kind == "hip":
+                             "on (spx_bin_mean_medoid_stage); statuses checked before timing" +
+                             (", and bit-identical to spx_bin_mean + spx_medoid" if args.full else ""))
+    if args.dump_outputs and rank == 0:
+        if not hasattr(be, "dump"):
+            raise SystemExit("bench.py: --dump-outputs needs the HIP backend")
+        last = bufs[(args.steps - 1) % len(bufs)]  # what the last timed step wrote (this rank's clusters)
+        out["config"]["dumped"] = be.dump(batch, last[0], last[1], args.dump_outputs, args.seed)
+    if be.kind == "hip" and args.full:
         kernel_lines(args, rank, world, out, be, batch, bm, md, separate, kept)
     del bm, md, separate, bufs, batch, t
     if be.kind == "hip":
@@ -996,13 +1056,15 @@ def main():
     world0 = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and world0 != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world0}")
-    want_cpu = world0 == 1 and not args.no_cpu_baseline and args.cpu_sample > 0
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    want_cpu = args.full and world0 == 1 and not args.no_cpu_baseline and args.cpu_sample > 0
     cpu_par = cpu_baseline_parallel(4 * args.cpu_sample, args.seed) if want_cpu else None
     be = make_backend(int(os.environ.get("LOCAL_RANK", "0")))
     rank, world, local = dist_init(be)
     out = {}
     headline(args, rank, world, local, out, be)
-    if rank == 0 and world == 1 and not args.no_extras and be.kind == "hip":
+    if args.full and rank == 0 and world == 1 and not args.no_extras and be.kind == "hip":
         config3(args, out)
         bin_mean_shapes(args, out)
         medoid_shapes(args, out)

@@ -57,7 +57,7 @@ class OracleBackend:
     def _run(self, csr):
         return _Consensus(c_oracle.bin_mean(csr)), _Medoid(c_oracle.medoid(csr))
 
-    def first_step(self, csr):
+    def first_step(self, csr, compare=True):
         bm, md = self._run(csr)
         assert not bool((bm.status != 0).any()) and not bool((md.rep < 0).any())
         return bm, md, None

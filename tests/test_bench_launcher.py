@@ -42,7 +42,7 @@ def test_bench_gpus_n_spawns_ranks(n):
     assert a["ok"] and a["reps_resolved"] and a["sample_equal_world1"] and a["clusters"] == 61
     assert a["consensus_peaks"] == a["planned_peaks"] == cfg["gathered_peaks_per_step"]
     assert cfg["gather_wire"].startswith("f32 bin sums")
-    assert d["value"] > 0 and d["steps"] == 2 and d["warmup"] == 1
+    assert d["value"] > 0 and d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
 
 
 def test_bench_worker_failure_is_nonzero():

@@ -13,7 +13,7 @@ timeout -k 10 300 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout
   > "$out/${tag}_gpu_tests.txt" 2>&1
 timeout -k 10 120 python -c 'import __graft_entry__ as g; g.smoke(); print("SMOKE OK")' \
   > "$out/${tag}_smoke.txt" 2>&1
-timeout -k 10 400 python bench.py > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
+timeout -k 10 600 python bench.py --full >"$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
 cd /tmp
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$out/prof_${tag}" -o run --output-format csv \
