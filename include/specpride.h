@@ -21,6 +21,8 @@
  *                       (called per cluster from best_spectrum():170-174)
  *   spx_compact_peaks   (packing helper for the shims' output writers)
  *   spx_wire_pack / spx_wire_unpack  (9-byte consensus peaks for the multi-GPU gather to rank 0)
+ *   spx_parse_mgf_text  (no reference counterpart: the number parsing of the MGF readers,
+ *                       binning.py:122-167 and the pyteomics-shaped one, moved to the device)
  *   spx_copy_h2d / spx_copy_d2h  (host transfers of pageable batches: the reference
  *                       holds its spectra in host memory, binning.py:122-167)
  *
@@ -283,6 +285,34 @@ int spx_wire_unpack(const float *mi, const void *count, int32_t count_bytes, int
  * returns with dst_host complete (after the work already on `stream`). */
 int spx_copy_h2d(void *dst_device, const void *src_host, size_t nbytes, void *stream);
 int spx_copy_d2h(void *dst_host, const void *src_device, size_t nbytes, void *stream);
+
+/* ---- device-side MGF ingest: the raw text of an MGF file, resident in HBM, parsed
+ *      straight into the cluster-segmented CSR.  The caller indexes
+ *      the file on the host (spx_mgf_index of spx_mgf.h: byte range and peak-line count
+ *      per record) and lists the records in destination order: record r is bytes
+ *      [rec_begin[r], rec_end[r]) of text, its peaks go to mz/inten[spec_off[r] ..
+ *      spec_off[r+1]) (spec_off = the prefix sum of the index's peak counts in that
+ *      order), its precursor fields to prec_mz/charge/rt/flags[r].  general: 0 the
+ *      binning.py grammar (a record starts at its TITLE= line), 1 the pyteomics-shaped
+ *      one (BEGIN IONS).  flags: bit0 PEPMASS, bit1 CHARGE, general also bit2
+ *      RTINSECONDS, bit3 TITLE present; absent prec_mz / rt are NaN, absent charge 0;
+ *      rt is NaN in the binning grammar.
+ *      rec_status[r] is SPX_MGF_OK -- every value of the record equals what the host
+ *      parser (spx_mgf_parse_ranges, i.e. Python float()) gives, bit for bit -- or
+ *      SPX_MGF_REPARSE: the record is outside the subset the kernel decides with
+ *      certainty (a sign, an exponent, nan/inf, more than 19 significant digits, a
+ *      repeated or lower-case key, text after END IONS, a byte >= 0x80, a peak-line
+ *      count other than its slot, a byte range outside text, a slot outside n_peaks,
+ *      ...); its outputs are undefined and the caller parses it on the host.  Peaks
+ *      are only ever written inside the record's own slot.
+ *      All pointers are device pointers; sizes that can be checked on the host
+ *      (negative, null arrays, general not 0/1) return SPX_EINVAL without a launch,
+ *      the ranges themselves live in device memory and are checked per record. */
+typedef enum spx_mgf_status { SPX_MGF_OK = 0, SPX_MGF_REPARSE = 1 } spx_mgf_status;
+int spx_parse_mgf_text(const void *text, int64_t text_len, const int64_t *rec_begin, const int64_t *rec_end,
+                       const int64_t *spec_off, int64_t n_records, int64_t n_peaks, int32_t general, double *mz,
+                       double *inten, double *prec_mz, int32_t *charge, double *rt, int32_t *flags,
+                       int32_t *rec_status, void *stream);
 
 int spx_abi_version(void);
 const char *spx_last_error(void); /* thread-local text of the last failure */

@@ -67,6 +67,7 @@ class SpxCosineParams(ctypes.Structure):
 EXPORTED = ["spx_bin_mean_workspace_size", "spx_bin_mean", "spx_bin_mean_stage", "spx_gap_average_workspace_size", "spx_gap_average",
             "spx_medoid_workspace_size", "spx_medoid_needs_large_path", "spx_medoid", "spx_bin_mean_medoid", "spx_bin_mean_medoid_stage", "spx_xcorr_distance", "spx_binned_cosine_workspace_size", "spx_binned_cosine", "spx_best_score",
             "spx_compact_peaks", "spx_wire_pack", "spx_wire_unpack", "spx_copy_h2d", "spx_copy_d2h",
+            "spx_parse_mgf_text",
             "spx_abi_version", "spx_last_error", "spx_profile_enable", "spx_profile_read",
             "spx_medoid_gram_operand_bits"]
 
@@ -152,7 +153,9 @@ def lib():
                            ("spx_bin_mean_medoid_stage",
                             [_p, _p, _p, _p, _p, _p, _p, _p, _sz, _p, _p, _p, _p, _sz, _p, _i32, _p]),
                            ("spx_profile_enable", [_i32]), ("spx_profile_read", [ctypes.c_char_p, _p, _p]),
-                           ("spx_medoid_gram_operand_bits", [])):
+                           ("spx_medoid_gram_operand_bits", []),
+                           ("spx_parse_mgf_text",
+                            [_p, _i64, _p, _p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p])):
         if hasattr(L, name):
             getattr(L, name).argtypes = argtypes
     if L.spx_abi_version() != SPX_ABI_VERSION:

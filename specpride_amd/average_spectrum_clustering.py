@@ -194,11 +194,17 @@ def _native_pass(fname, get_cluster=get_cluster_id, get_pepmass=naive_average_ma
     rt_mode = {median_rt: "median", lower_median_mass_rt: "mass_lower_median"}.get(get_rt)
     if pm_mode is None or rt_mode is None or get_cluster is not get_cluster_id:
         return None
-    native = _native_runs(fname)
-    if native is None:
-        return None
-    ids, csr = native
-    r = engine.gap_average(engine.DeviceBatch.from_host(csr), kwargs.get("mz_accuracy", DIFF_THRESH),
+    from . import device_ingest, mgf_native
+
+    got = device_ingest.load(fname, True, mgf_native.GROUP_RUNS) if device_ingest.enabled() else None
+    if got is not None:  # opt-in: the MGF text is parsed on the device
+        batch, ids = got[0], got[1]["ids"]
+    else:
+        native = _native_runs(fname)
+        if native is None:
+            return None
+        ids, batch = native[0], engine.DeviceBatch.from_host(native[1])
+    r = engine.gap_average(batch, kwargs.get("mz_accuracy", DIFF_THRESH),
                            kwargs.get("dyn_range", DYN_RANGE), kwargs.get("min_fraction", MIN_FRACTION),
                            pepmass=pm_mode, rt=rt_mode).to_host()
     return ids, r

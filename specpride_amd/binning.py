@@ -147,7 +147,11 @@ class RepresentativeSpectrumCreator:
         """The device pass over a packed batch: the dense host result of
         :meth:`engine.PeaksResult.to_host`, after raising the reference's error for
         the first failing cluster (AssertionError on mixed charges, binning.py:205-206)."""
-        batch = engine.DeviceBatch.from_host(csr, self.device)
+        return self._combine_batch(engine.DeviceBatch.from_host(csr, self.device), minimum, maximum, binsize,
+                                   apply_peak_quorum)
+
+    def _combine_batch(self, batch, minimum=100, maximum=2000, binsize=0.02, apply_peak_quorum=True):
+        """:meth:`_combine_host` over a batch already in HBM."""
         # a batch small enough for the one-copy readback (the per-cluster calls) runs
         # the large-cluster chain only if a cluster needs it (spx_bin_mean_stage)
         res = engine.bin_mean(batch, minimum, maximum, binsize, apply_peak_quorum,
@@ -258,6 +262,17 @@ def _main_mgf(mgf_file, out, verbose):
 
     rsc = RepresentativeSpectrumCreator(verbose=verbose)
     print("Reading spectra...")
+    from . import device_ingest
+
+    if device_ingest.enabled():  # opt-in: the MGF text is parsed on the device
+        got = device_ingest.load(mgf_file, False, mgf_native.GROUP_BINNING, rsc.device)
+        if got is not None:
+            batch, meta = got
+            print("Clustering...")
+            res = rsc._combine_batch(batch, minimum=100, maximum=2000, binsize=0.02)
+            mgf_native.write_records(out, mgf_native.STYLE_BINNING, meta["ids"], res["out_off"], res["out_mz"],
+                                     res["out_int"], res["prec"], res["charge"])
+            return
     flat = _flat_clusters(mgf_file)
     if flat is not None:  # native parse straight to the cluster-segmented CSR, native writer
         ids, csr = flat

@@ -49,6 +49,7 @@
 #include "binned_cosine.hip"
 #include "gap_average.hip"
 #include "medoid.hip"
+#include "mgf_parse.hip"
 #include "fused.hip"
 #include "transfer.hip"
 #include "wire.hip"
@@ -1285,4 +1286,23 @@ extern "C" int spx_copy_d2h(void* dst_host, const void* src_device, size_t nbyte
     return SPX_EHIP;
   }
   return SPX_SUCCESS;
+}
+
+// ------------------------------------------------------------ device-side MGF ingest
+extern "C" int spx_parse_mgf_text(const void* text, int64_t text_len, const int64_t* rec_begin, const int64_t* rec_end,
+                                  const int64_t* spec_off, int64_t n_records, int64_t n_peaks, int32_t general,
+                                  double* mz, double* inten, double* prec_mz, int32_t* charge, double* rt,
+                                  int32_t* flags, int32_t* rec_status, void* stream) {
+  if (text_len < 0 || n_records < 0 || n_peaks < 0) return fail(SPX_EINVAL, "spx_parse_mgf_text: negative size");
+  if (general != 0 && general != 1) return fail(SPX_EINVAL, "spx_parse_mgf_text: general must be 0 or 1");
+  if ((text_len > 0 && !text) || (n_peaks > 0 && (!mz || !inten)))
+    return fail(SPX_EINVAL, "spx_parse_mgf_text: null text or peak array");
+  if (n_records > 0 && (!rec_begin || !rec_end || !spec_off || !prec_mz || !charge || !rt || !flags || !rec_status))
+    return fail(SPX_EINVAL, "spx_parse_mgf_text: null record array");
+  if (n_records == 0) return SPX_SUCCESS;
+  const unsigned grid = (unsigned)std::min<int64_t>(n_records, int64_t(1) << 20);
+  hipLaunchKernelGGL(spx::mgf_parse_kernel, dim3(grid), dim3(spx::kMgfBlock), 0, reinterpret_cast<hipStream_t>(stream),
+                     static_cast<const uint8_t*>(text), text_len, rec_begin, rec_end, spec_off, n_records, n_peaks,
+                     (int)general, mz, inten, prec_mz, charge, rt, flags, rec_status);
+  return check_launch("mgf_parse_kernel");
 }

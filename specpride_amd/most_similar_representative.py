@@ -135,8 +135,10 @@ def _main_native(inputfile, outputfile):
     cluster scan done natively (spx_mgf_group mode 2), the chosen records written
     from the flat arrays.  False when the file is outside the native subset or a
     record has no TITLE (the dict path then decides)."""
-    from . import ingest, mgf_native
+    from . import device_ingest, ingest, mgf_native
 
+    if device_ingest.enabled() and _main_device(inputfile, outputfile):
+        return True
     try:
         flat = mgf_native.parse_general(inputfile, group=mgf_native.GROUP_FIRST_RUNS)
     except ValueError:
@@ -153,6 +155,28 @@ def _main_native(inputfile, outputfile):
     print("".join(f"{cl}\n{n}\n" for cl, n in zip(ids, sizes.tolist())), end="")
     print(len(ids))
     write_chosen(outputfile, flat, records[rep])
+    return True
+
+
+def _main_device(inputfile, outputfile):
+    """:func:`_main_native` with the MGF text parsed on the device (opt-in,
+    ``SPX_DEVICE_INGEST=1``): the same cluster scan, prints and output.  False when
+    the file is outside the native subset as a whole (the host paths then decide)."""
+    from . import device_ingest, mgf_native
+
+    got = device_ingest.load(inputfile, True, mgf_native.GROUP_FIRST_RUNS)
+    if got is None:
+        return False
+    batch, meta = got
+    rep, _ = engine.medoid(batch, TOLERANCE).to_host()
+    if np.any(rep < 0):
+        raise RuntimeError("medoid engine could not resolve a cluster (see DESIGN.md limits)")
+    ids, sizes = meta["ids"], meta["sizes"]
+    print("".join(f"{cl}\n{n}\n" for cl, n in zip(ids, sizes.tolist())), end="")
+    print(len(ids))
+    titles, off, mz, inten, prec, charge, rt, flags = device_ingest.chosen_records(batch, meta, rep)
+    mgf_native.write_records(outputfile, mgf_native.STYLE_MEDOID, titles, off, mz, inten, prec, charge, rt,
+                             flags | mgf_native.FLAG_TITLE)
     return True
 
 
