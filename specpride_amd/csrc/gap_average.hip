@@ -14,10 +14,16 @@
 //   * the sorted gap between two consecutive occupied buckets is exactly
 //     fl(min(next) - max(prev)) -- the same f64 subtraction np.diff performs.
 // So group boundaries and group counts are exact (integer/bit-exact), and only
-// the group sums differ from the reference's cumsum differences by rounding
-// (within 1e-12 relative; the parity bar is 1e-5).  The sums are accumulated
-// as 64-bit fixed point (scale 2^e per cluster from max|value| * #peaks), so
-// LDS integer atomics make them order-independent and run-to-run deterministic.
+// the group sums differ from the reference's cumsum differences by rounding.
+// The sums are accumulated as 64-bit fixed point, so LDS integer atomics make
+// them order-independent and run-to-run deterministic.  The adds are exact; each
+// value is rounded to the scale's quantum before its add.  The scale is 2^e per
+// cluster from max|value| * #peaks where gap_emit finds that within 2^-31 of every
+// group it may emit (typical data: 1e-12 relative), else one scale per group from
+// the group's own max|value| * count (the global kernel: at most count^2 * 2^-61
+// relative for same-sign values) -- see "The fixed-point sums' scales" below.  The
+// tiled giant pipeline sums at the one scale per cluster, applies the same test in its
+// step 6b, and runs a giant that fails it again through gap_body in its step-6 workgroup.
 //
 //   1  block reduce: min/max m/z, max |intensity|, finiteness
 //   2  bucket bitmap (ds_or_b64) -> exclusive popcount prefix -> slot ids
@@ -584,17 +590,67 @@ __device__ __forceinline__ int32_t gap_groups(const GapState<PrefixT>& S, const 
   return kOk;
 }
 
+// The fixed-point sums' scales.  The integer adds are exact; each value is rounded to the
+// scale's quantum before its add, so a group sum of `count` values is off by at most
+// count / 2 quanta.  One scale per cluster (2^61 / (max|value| * #peaks), the fast path)
+// makes that error a fraction of the cluster's LARGEST value: gap_emit checks it against
+// every group it may emit, and a cluster where it passes kGapTol of a group's own sum
+// (one huge peak beside small kept groups, a group near m/z 0 beside far ones) is summed
+// again with one scale per group (2^61 / (the group's max|value| * its count)): there the
+// relative error of an emitted value is at most count^2 * 2^-61 for same-sign values,
+// whatever the other groups hold and whatever dyn_range is.  The LDS and wide kernels
+// hand such a cluster on (kDeferred); the global kernel's bodies do the second sum, the
+// per-group exponents packed into the slice's flags words (bits 8..31; the non-finite
+// classes keep bits 0..5).
+constexpr int32_t kGapCoarse = 101;   // gap_emit, internal: the cluster's one scale is too coarse
+constexpr double kGapTol = 0x1p-31;   // 4.7e-10: with the divisions' roundings, within 1e-9 by construction
+__device__ __forceinline__ uint32_t gap_pack_exps(int ex_m, int ex_i) {
+  return ((uint32_t)(ex_m + 2048) << 20) | ((uint32_t)(ex_i + 2048) << 8);
+}
+__device__ __forceinline__ int gap_sc_m(uint32_t w) { return 61 - ((int)(w >> 20) - 2048); }
+__device__ __forceinline__ int gap_sc_i(uint32_t w) { return 61 - ((int)((w >> 8) & 0xfffu) - 2048); }
+// max |x| by integer atomicMax: the bits of a non-negative double order like the values
+__device__ __forceinline__ unsigned long long gap_abs_bits(double x) {
+  return (unsigned long long)__double_as_longlong(fabs(x));
+}
+
+// The m/z half of gap_emit's test, once per cluster: a group's m/z sum is at least count
+// times the cluster's smallest |m/z| (0 if the m/z straddle 0), its error at most count
+// half quanta -- so half a quantum within kGapTol of that floor covers every group.
+__device__ __forceinline__ int gap_mz_coarse(double lo, double hi, int sc_m) {
+  const double mz_floor = lo > 0.0 ? lo : (hi < 0.0 ? -hi : 0.0);
+  return !(ldexp(0.5, -sc_m) <= kGapTol * mz_floor);
+}
+// The intensity scale of a cluster whose intensities are all 0.0: the sums are exactly 0 at
+// any scale, and at this one the quantum underflows to 0, so gap_emit's test sees no error
+// (61 - exponent(0) would claim half of 2^-61 per peak and send the cluster down the chain)
+constexpr int kGapZeroScale = 4000;
+// Bucket indices are int64 conversions of m/z / bucket_w: supported while |m/z| / bucket_w
+// stays below 2^62 (2.3e16 Da at the global path's 0.005-Da buckets); a cluster past that
+// is deferred before any index is formed.
+__device__ __forceinline__ bool gap_mz_indexable(double lo, double hi, const GapParams& P) {
+  return fmax(fabs(lo), fabs(hi)) * P.inv_bucket_w < 0x1p62;
+}
+
 // 6: min_fraction filter, dynamic range, ordered output of cluster c's E groups
-// (fixed-point sums at scales 2^sc_m / 2^sc_i): kOk or kEmpty.
-template <bool kL, class PrefixT>
+// (fixed-point sums at scales 2^sc_m / 2^sc_i, or with kPG at each group's own scales in
+// S.flags): kOk or kEmpty -- or, without kPG, kGapCoarse and nothing written.
+template <bool kL, class PrefixT, bool kPG = false>
 __device__ __forceinline__ int32_t gap_emit(const GapState<PrefixT>& S, const GapParams& P, int64_t c, int64_t n,
-                                            int64_t N, int64_t p0, int E, int sc_m, int sc_i, const PeaksOut& out,
-                                            int* tmp, double* red, int* votes) {
+                                            int64_t N, int64_t p0, int E, int sc_m, int sc_i, int coarse_m,
+                                            const PeaksOut& out, int* tmp, double* red, int* votes) {
   const int tid = threadIdx.x, lane = lane_id(), wid = wave_id();
   const double min_len = P.min_fraction * (double)n;
   const int gper = (E + GA_BLOCK - 1) / GA_BLOCK;
   const int e0 = tid * gper;
-  auto isum = [&](int e) -> double { return ldexp((double)(int64_t)S.kmax[e], -sc_i); };
+  auto isum = [&](int e) -> double {
+    if constexpr (kPG) return ldexp((double)(int64_t)S.kmax[e], -gap_sc_i(S.flags[e]));
+    else return ldexp((double)(int64_t)S.kmax[e], -sc_i);
+  };
+  auto msum = [&](int e) -> double {
+    if constexpr (kPG) return ldexp((double)(int64_t)S.kmin[e], -gap_sc_m(S.flags[e]));
+    else return ldexp((double)(int64_t)S.kmin[e], -sc_m);
+  };
   double gmax = -__longlong_as_double(0x7ff0000000000000ll);
   int anyg = 0;
   for (int j = 0; j < gper; ++j) {
@@ -609,25 +665,85 @@ __device__ __forceinline__ int32_t gap_emit(const GapState<PrefixT>& S, const Ga
   if (!block_any<GA_BLOCK, kL>(anyg, votes, 1)) return kEmpty;
   for (int w = 0; w < GA_BLOCK / kWave; ++w) gmax = fmax(gmax, red[w]);
   const double thr = gmax / P.dyn_range;
-  int mine = 0;
+  // The one scale's rounding error against what may be emitted (all powers of two and
+  // products: scaling every intensity by 2^k scales both sides alike).  Intensities: a
+  // group whose sum could reach the threshold with its error (count / 2 quanta) added may
+  // be emitted, and the error must stay within kGapTol of that sum.  m/z: coarse_m, the
+  // caller's one test for the whole cluster (gap_mz_coarse).
+  const double thr_n = thr * (double)n, thr_lo = thr_n - fabs(thr_n) * 0x1p-30;
+  const double hq_i = ldexp(0.5, -sc_i);
+  int mine = 0, coarse = 0;
+  if constexpr (!kPG) coarse = coarse_m;
   for (int j = 0; j < gper; ++j) {
     const int e = e0 + j;
-    if (e < E && (double)S.gcnt[e] >= min_len && isum(e) / (double)n >= thr) ++mine;
+    if (e < E && (double)S.gcnt[e] >= min_len) {
+      const double si = isum(e);
+      if (si / (double)n >= thr) ++mine;
+      if constexpr (!kPG) {
+        const double err = (double)S.gcnt[e] * hq_i;
+        coarse |= si + err >= thr_lo && err > kGapTol * fabs(si);
+      }
+    }
   }
   int total;
-  int o = block_exclusive_scan<GA_BLOCK, int, kL>(mine, tmp, total);
+  int o;
+  if constexpr (!kPG && kL) {
+    // the verdict rides the scan (an LDS kernel's groups are fewer than 2^16): no barrier of its own
+    o = block_exclusive_scan<GA_BLOCK, int, kL>(mine | (coarse << 16), tmp, total);
+    if (total >> 16) return kGapCoarse;
+    o &= 0xffff;
+  } else {
+    if constexpr (!kPG) {
+      if (block_any<GA_BLOCK, kL>(coarse, votes, 0)) return kGapCoarse;
+    }
+    o = block_exclusive_scan<GA_BLOCK, int, kL>(mine, tmp, total);
+  }
   for (int j = 0; j < gper; ++j) {
     const int e = e0 + j;
     if (e >= E || (double)S.gcnt[e] < min_len) continue;
     const double iv = isum(e) / (double)n;
     if (!(iv >= thr)) continue;
     SPX_GUARD(o < N, "gap out c=%ld o=%d N=%ld\n", (long)c, o, (long)N)
-    out.mz[p0 + o] = ldexp((double)(int64_t)S.kmin[e], -sc_m) / (double)S.gcnt[e];
+    out.mz[p0 + o] = msum(e) / (double)S.gcnt[e];
     out.inten[p0 + o] = iv;
     ++o;
   }
   if (tid == 0) out.count[c] = total;
   return kOk;
+}
+
+// 5 with one scale per group (global scratch): each group's max |m/z| and max |intensity|,
+// from them and its count the exponents (S.flags; the sum of gcnt values of at most that
+// size stays below 2^61), then the sums at those scales.  each(f) calls f(m, it, group)
+// for every peak of the cluster; call with the whole block, ends with a barrier.
+template <class Each>
+__device__ __forceinline__ void gap_sums_per_group(const GapState<uint32_t>& S, int E, Each each) {
+  const int tid = threadIdx.x;
+  for (int e = tid; e < E; e += GA_BLOCK) { S.kmin[e] = 0ull; S.kmax[e] = 0ull; }
+  __syncthreads();
+  each([&](double m, double it, uint32_t eg) {
+    atomicMax(reinterpret_cast<unsigned long long*>(&S.kmin[eg]), gap_abs_bits(m));
+    atomicMax(reinterpret_cast<unsigned long long*>(&S.kmax[eg]), gap_abs_bits(it));
+  });
+  __syncthreads();
+  for (int e = tid; e < E; e += GA_BLOCK) {
+    const double cnt = (double)S.gcnt[e];
+    int gm, gi;
+    frexp(__longlong_as_double((long long)S.kmin[e]) * cnt, &gm);
+    frexp(__longlong_as_double((long long)S.kmax[e]) * cnt, &gi);
+    S.flags[e] = gap_pack_exps(gm, gi);
+    S.kmin[e] = 0ull;
+    S.kmax[e] = 0ull;
+  }
+  __syncthreads();
+  each([&](double m, double it, uint32_t eg) {
+    const uint32_t w = S.flags[eg];
+    atomicAdd(reinterpret_cast<unsigned long long*>(&S.kmin[eg]),
+              (unsigned long long)__double2ll_rn(ldexp(m, gap_sc_m(w))));
+    atomicAdd(reinterpret_cast<unsigned long long*>(&S.kmax[eg]),
+              (unsigned long long)__double2ll_rn(ldexp(it, gap_sc_i(w))));
+  });
+  __syncthreads();
 }
 
 // --------------------------------------------------------------- the body
@@ -823,6 +939,7 @@ __device__ int32_t gap_body(const CsrView& v, const GapParams& P, const GapState
     hi = fmax(hi, red[GA_NW + w]);
     imax = fmax(imax, red[2 * GA_NW + w]);
   }
+  if (!gap_mz_indexable(lo, hi, P)) return kDeferred;
   const int64_t kb = floor_div_exact(lo, P.bucket_w, P.inv_bucket_w);
   const int64_t ke = floor_div_exact(hi, P.bucket_w, P.inv_bucket_w);
   const int64_t nw = (ke - kb) / 64 + 1;
@@ -968,20 +1085,35 @@ __device__ int32_t gap_body(const CsrView& v, const GapParams& P, const GapState
   int ex_m, ex_i;
   frexp(fmax(fabs(lo), fabs(hi)) * (double)N, &ex_m);
   frexp(imax * (double)N, &ex_i);
-  const int sc_m = 61 - ex_m, sc_i = 61 - ex_i;
-  peaks([&](double m, double it, int32_t& tag, auto reg_c) {
+  const int sc_m = 61 - ex_m, sc_i = imax == 0.0 ? kGapZeroScale : 61 - ex_i;
+  const int coarse_m = gap_mz_coarse(lo, hi, sc_m);
+  auto group_of = [&](double m, int32_t tag, auto reg_c) __attribute__((always_inline)) -> uint32_t {
     const int slot = decltype(reg_c)::value
                          ? tag
                          : bitmap_rank(S.bitmap, S.wprefix, floor_div_exact(m, P.bucket_w, P.inv_bucket_w) - kb);
     const uint32_t eg = S.cnt[slot];
     SPX_GUARD(slot >= 0 && slot < D && (int)eg < E, "gap eg c=%ld slot=%d eg=%u E=%d\n", (long)c, slot, eg, E)
+    return eg;
+  };
+  peaks([&](double m, double it, int32_t& tag, auto reg_c) {
+    const uint32_t eg = group_of(m, tag, reg_c);
     atomicAdd(reinterpret_cast<unsigned long long*>(&S.kmin[eg]), (unsigned long long)__double2ll_rn(ldexp(m, sc_m)));
     atomicAdd(reinterpret_cast<unsigned long long*>(&S.kmax[eg]), (unsigned long long)__double2ll_rn(ldexp(it, sc_i)));
   });
   bar();
 
   SPX_GA_STAMP(6);
-  return gap_emit<kL>(S, P, c, n, N, p0, E, sc_m, sc_i, out, tmp, red, votes);
+  const int32_t st = gap_emit<kL>(S, P, c, n, N, p0, E, sc_m, sc_i, coarse_m, out, tmp, red, votes);
+  if (st != kGapCoarse) return st;
+  // the cluster's one scale is too coarse for a group it may emit (gap_emit)
+  if constexpr (kL) {
+    return kDeferred;  // down the chain: the global kernel sums it again
+  } else {
+    gap_sums_per_group(S, E, [&](auto f) __attribute__((always_inline)) {
+      peaks([&](double m, double it, int32_t& tag, auto reg_c) { f(m, it, group_of(m, tag, reg_c)); });
+    });
+    return gap_emit<kL, PrefixT, true>(S, P, c, n, N, p0, E, 0, 0, 0, out, tmp, red, votes);
+  }
 }
 
 template <class PrefixT>
@@ -1153,6 +1285,9 @@ struct GapGiant {  // zeroed by the call's memset
   // as gap_body_nf restates it): any NaN/inf m/z or intensity; the -inf, +inf and NaN m/z counts; the true
   // groups' count M (the -inf group, the finite gaps' groups, the +inf boundary) and the -inf group's b0
   int32_t nf, n_ninf, n_pinf, n_nan, M, b0;
+  // step 6b: the one scale per cluster is too coarse for a group that may be emitted (gap_emit's test):
+  // step 6 then runs the whole giant in one workgroup, with one scale per group
+  int32_t coarse, pad2;
 };
 
 // Pass 5 of a giant with more groups than the LDS pre-sum holds: each tile's hashed
@@ -1277,10 +1412,10 @@ __device__ int32_t gap_body_nf(const CsrView& v, const GapParams& P, const GapSt
   }
   if (N < 2) return kNoGap;
 
-  // 1: the finite m/z extent, max |finite intensity|, the non-finite m/z classes
-  double lo = INF, hi = -INF, imax = 0.0;
+  // 1: the finite m/z extent, the non-finite m/z classes
+  double lo = INF, hi = -INF;
   int cn = 0, cp = 0, cq = 0;
-  gap_peaks<true>(v, p0, p1, [&](int64_t, double m, double it) {
+  gap_peaks<false>(v, p0, p1, [&](int64_t, double m, double) {
     if (isfinite(m)) {
       lo = fmin(lo, m);
       hi = fmax(hi, m);
@@ -1291,12 +1426,10 @@ __device__ int32_t gap_body_nf(const CsrView& v, const GapParams& P, const GapSt
     } else {
       ++cn;
     }
-    if (isfinite(it)) imax = fmax(imax, fabs(it));
   });
   lo = wave_min_dpp(lo);
   hi = wave_max_dpp(hi);
-  imax = wave_max_dpp(imax);
-  if (lane == 0) { red[wid] = lo; red[GA_NW + wid] = hi; red[2 * GA_NW + wid] = imax; }
+  if (lane == 0) { red[wid] = lo; red[GA_NW + wid] = hi; }
   int n_ninf, n_pinf, n_nan;
   block_exclusive_scan<GA_BLOCK, int>(cn, tmp, n_ninf);  // its barriers order red too
   block_exclusive_scan<GA_BLOCK, int>(cp, tmp, n_pinf);
@@ -1304,7 +1437,6 @@ __device__ int32_t gap_body_nf(const CsrView& v, const GapParams& P, const GapSt
   for (int w = 0; w < GA_NW; ++w) {
     lo = fmin(lo, red[w]);
     hi = fmax(hi, red[GA_NW + w]);
-    imax = fmax(imax, red[2 * GA_NW + w]);
   }
   __syncthreads();
   const int64_t Nf = N - n_ninf - n_pinf - n_nan;
@@ -1315,6 +1447,7 @@ __device__ int32_t gap_body_nf(const CsrView& v, const GapParams& P, const GapSt
   const double acc = P.mz_accuracy;
   auto key = [&](const uint64_t* a, int d) { return f64_from_order_key(a[d]); };
   if (Nf > 0) {  // uniform
+    if (!gap_mz_indexable(lo, hi, P)) return kDeferred;
     kb = floor_div_exact(lo, P.bucket_w, P.inv_bucket_w);
     const int64_t nw = (floor_div_exact(hi, P.bucket_w, P.inv_bucket_w) - kb) / 64 + 1;
     if (nw > S.wcap) return kDeferred;
@@ -1397,24 +1530,45 @@ __device__ int32_t gap_body_nf(const CsrView& v, const GapParams& P, const GapSt
   for (int e = tid; e < E; e += GA_BLOCK) { S.kmin[e] = 0ull; S.kmax[e] = 0ull; }
   __syncthreads();
 
-  // 5: fixed-point sums of the finite values, the non-finite m/z's counts, the classes
-  int ex_m, ex_i;
-  frexp(Nf > 0 ? fmax(fabs(lo), fabs(hi)) * (double)N : 0.0, &ex_m);
-  frexp(imax * (double)N, &ex_i);
-  const int sc_m = 61 - ex_m, sc_i = 61 - ex_i;
+  // 5: fixed-point sums of the finite values, the non-finite m/z's counts, the classes.
+  // One scale per group, always (this body is rare): each group's max |finite m/z| and
+  // max |finite intensity| first, then its exponents into the flags words' upper bits
+  // (gap_pack_exps; a group holds at most its finite m/z plus every non-finite one)
+  auto group_of = [&](double m) -> int {
+    if (isfinite(m))
+      return (int)S.cnt[bitmap_rank(S.bitmap, S.wprefix, floor_div_exact(m, P.bucket_w, P.inv_bucket_w) - kb)];
+    return emitted(m == -INF ? 0 : M);  // -inf: group 0; +inf and NaN: the last true group
+  };
+  gap_peaks<true>(v, p0, p1, [&](int64_t, double m, double it) {
+    const int eg = group_of(m);
+    if (isfinite(m)) atomicMax(reinterpret_cast<unsigned long long*>(&S.kmin[eg]), gap_abs_bits(m));
+    if (isfinite(it)) atomicMax(reinterpret_cast<unsigned long long*>(&S.kmax[eg]), gap_abs_bits(it));
+  });
+  __syncthreads();
+  for (int e = tid; e < E; e += GA_BLOCK) {
+    const double cnt = (double)S.gcnt[e] + (double)(n_ninf + n_pinf + n_nan);
+    int gm, gi;
+    frexp(__longlong_as_double((long long)S.kmin[e]) * cnt, &gm);
+    frexp(__longlong_as_double((long long)S.kmax[e]) * cnt, &gi);
+    S.flags[e] = gap_pack_exps(gm, gi);
+    S.kmin[e] = 0ull;
+    S.kmax[e] = 0ull;
+  }
+  __syncthreads();
   gap_peaks<true>(v, p0, p1, [&](int64_t, double m, double it) {
     uint32_t fl = 0u;
-    int eg;
+    const int eg = group_of(m);
+    const uint32_t w = S.flags[eg];  // (its upper bits: the classes below only OR into bits 0..5)
     if (isfinite(m)) {
-      eg = (int)S.cnt[bitmap_rank(S.bitmap, S.wprefix, floor_div_exact(m, P.bucket_w, P.inv_bucket_w) - kb)];
-      atomicAdd(reinterpret_cast<unsigned long long*>(&S.kmin[eg]), (unsigned long long)__double2ll_rn(ldexp(m, sc_m)));
+      atomicAdd(reinterpret_cast<unsigned long long*>(&S.kmin[eg]),
+                (unsigned long long)__double2ll_rn(ldexp(m, gap_sc_m(w))));
     } else {
-      eg = emitted(m == -INF ? 0 : M);  // -inf: group 0; +inf and NaN: the last true group
       atomicAdd(&S.gcnt[eg], 1u);
       fl = isnan(m) ? NF_MZ_NAN : (m > 0.0 ? NF_MZ_PINF : NF_MZ_NINF);
     }
     if (isfinite(it))
-      atomicAdd(reinterpret_cast<unsigned long long*>(&S.kmax[eg]), (unsigned long long)__double2ll_rn(ldexp(it, sc_i)));
+      atomicAdd(reinterpret_cast<unsigned long long*>(&S.kmax[eg]),
+                (unsigned long long)__double2ll_rn(ldexp(it, gap_sc_i(w))));
     else
       fl |= (isnan(it) ? NF_MZ_NAN : (it > 0.0 ? NF_MZ_PINF : NF_MZ_NINF)) << 3;
     if (fl) atomicOr(&S.flags[eg], fl);
@@ -1434,8 +1588,8 @@ __device__ int32_t gap_body_nf(const CsrView& v, const GapParams& P, const GapSt
   const double min_len = P.min_fraction * (double)n;
   auto values = [&](int e, uint32_t pf, double& vm, double& vi) {
     const uint32_t gf = S.flags[e];
-    vm = nf_value(pf, gf, ldexp((double)(int64_t)S.kmin[e], -sc_m) / (double)S.gcnt[e]);
-    vi = nf_value(pf >> 3, gf >> 3, ldexp((double)(int64_t)S.kmax[e], -sc_i) / (double)n);
+    vm = nf_value(pf, gf, ldexp((double)(int64_t)S.kmin[e], -gap_sc_m(gf)) / (double)S.gcnt[e]);
+    vi = nf_value(pf >> 3, gf >> 3, ldexp((double)(int64_t)S.kmax[e], -gap_sc_i(gf)) / (double)n);
   };
   double gmax = -INF;
   int anyg = 0, gnan = 0;
@@ -1492,6 +1646,122 @@ __device__ int32_t gap_body_nf(const CsrView& v, const GapParams& P, const GapSt
   return kOk;
 }
 
+// ------------------------------------------------------ far m/z outliers
+// A finite cluster whose bucket range passes the slice's bitmap because of a few far
+// peaks (one m/z of 1e9 beside an ordinary spectrum): gap_body defers it, and the global
+// kernel runs this body before reporting it.  The peaks within the bitmap's reach of the
+// smallest m/z take buckets and slots as everywhere; each of the at most GA_FAR_MAX peaks
+// beyond gets a slot of its own behind them, in m/z order (equal m/z: the first of their
+// slots counts them, the others stay empty copies -- a zero gap, no peaks).  Slots are
+// still ascending m/z runs, so gap_groups and gap_emit apply unchanged; the sums take one
+// scale per group (gap_sums_per_group: the far m/z would coarsen a cluster-wide one).
+// kDeferred when the cluster is not of this kind (no far peak, too many, or gap_body's
+// other reasons: a bucket spanning mz_accuracy, more slots than the slice holds).
+constexpr int GA_FAR_MAX = 512;
+
+__device__ int32_t gap_body_far(const CsrView& v, const GapParams& P, const GapState<uint32_t>& S, int64_t c,
+                                const PeaksOut& out, int* tmp, double* red, int* votes) {
+  __shared__ double far_mz[GA_FAR_MAX], far_sorted[GA_FAR_MAX];
+  __shared__ int far_n;
+  const int tid = threadIdx.x, lane = lane_id(), wid = wave_id();
+  const int64_t s0 = v.cluster_off[c], s1 = v.cluster_off[c + 1], n = s1 - s0;
+  const int64_t p0 = v.spec_off[s0], p1 = v.spec_off[s1], N = p1 - p0;
+  const double INF = __longlong_as_double(0x7ff0000000000000ll);
+  if (n < 2 || N < 2) return kDeferred;  // (gap_body answers those itself)
+  // 1: the smallest m/z, then the largest within the bitmap's reach of it and the far count
+  double lo = INF;
+  int bad = 0;
+  gap_peaks<true>(v, p0, p1, [&](int64_t, double m, double it) {
+    bad |= !isfinite(m) || !isfinite(it);
+    lo = fmin(lo, m);
+  });
+  lo = wave_min_dpp(lo);
+  if (lane == 0) red[wid] = lo;
+  if (tid == 0) far_n = 0;
+  if (block_any<GA_BLOCK, false>(bad, votes, 0)) return kDeferred;
+  for (int w = 0; w < GA_NW; ++w) lo = fmin(lo, red[w]);
+  __syncthreads();
+  if (!gap_mz_indexable(lo, lo, P)) return kDeferred;
+  const int64_t kb = floor_div_exact(lo, P.bucket_w, P.inv_bucket_w);
+  const int64_t reach = (int64_t)S.wcap * 64;  // buckets
+  // a peak's bucket past the smallest one; `reach` for everything well beyond it, decided in
+  // double before any conversion (an m/z of 1e300 has no int64 bucket)
+  auto bucket = [&](double m) -> int64_t {
+    if ((m - lo) * P.inv_bucket_w >= (double)reach + 4.0) return reach;
+    return floor_div_exact(m, P.bucket_w, P.inv_bucket_w) - kb;
+  };
+  double hi = lo;
+  int nfar = 0;
+  gap_peaks<false>(v, p0, p1, [&](int64_t, double m, double) {
+    if (bucket(m) < reach) hi = fmax(hi, m);
+    else ++nfar;
+  });
+  hi = wave_max_dpp(hi);
+  if (lane == 0) red[wid] = hi;
+  int F;
+  block_exclusive_scan<GA_BLOCK, int>(nfar, tmp, F);  // its barriers order red too
+  for (int w = 0; w < GA_NW; ++w) hi = fmax(hi, red[w]);
+  __syncthreads();
+  if (F == 0 || F > GA_FAR_MAX) return kDeferred;
+  const int64_t nw = bucket(hi) / 64 + 1;  // <= S.wcap
+  for (int64_t w = tid; w < nw; w += GA_BLOCK) S.bitmap[w] = 0ull;
+  __syncthreads();
+  // 2: the near peaks' buckets; the far peaks' m/z collected
+  gap_peaks<false>(v, p0, p1, [&](int64_t, double m, double) {
+    const int64_t b = bucket(m);
+    if (b < reach) atomicOr(&S.bitmap[b >> 6], 1ull << (b & 63));
+    else far_mz[atomicAdd(&far_n, 1)] = m;
+  });
+  __syncthreads();
+  const int D0 = bitmap_prefix<GA_BLOCK, uint32_t, false>(S.bitmap, S.wprefix, (int)nw, tmp);
+  if ((int64_t)D0 + F > S.dcap) return kDeferred;
+  const int D = D0 + F;
+  for (int i = tid; i < F; i += GA_BLOCK) {  // F <= GA_BLOCK: stable ranks, one thread per far peak
+    const double x = far_mz[i];
+    int r = 0;
+    for (int j = 0; j < F; ++j) r += far_mz[j] < x || (far_mz[j] == x && j < i);
+    far_sorted[r] = x;
+  }
+  __syncthreads();
+  for (int d = tid; d < D; d += GA_BLOCK) {
+    const uint64_t k = d < D0 ? 0ull : f64_order_key(far_sorted[d - D0]);
+    S.cnt[d] = 0u;
+    S.gcnt[d] = 0u;
+    S.kmin[d] = d < D0 ? ~0ull : k;
+    S.kmax[d] = k;
+  }
+  __syncthreads();
+  auto slot_of = [&](double m) -> int {
+    const int64_t b = bucket(m);
+    if (b < reach) return bitmap_rank(S.bitmap, S.wprefix, b);
+    int a = 0, z = F;  // the first far slot holding m
+    while (a < z) {
+      const int h = (a + z) >> 1;
+      if (far_sorted[h] < m) a = h + 1;
+      else z = h;
+    }
+    return D0 + a;
+  };
+  // 3: per-slot count and m/z extent (a far slot's extent is its one value already)
+  gap_peaks<false>(v, p0, p1, [&](int64_t, double m, double) {
+    const int slot = slot_of(m);
+    SPX_GUARD(slot >= 0 && slot < D, "gap far slot c=%ld slot=%d D=%d\n", (long)c, slot, D)
+    atomicAdd(&S.cnt[slot], 1u);
+    if (slot < D0) {
+      const uint64_t key = f64_order_key(m);
+      atomicMin(reinterpret_cast<unsigned long long*>(&S.kmin[slot]), (unsigned long long)key);
+      atomicMax(reinterpret_cast<unsigned long long*>(&S.kmax[slot]), (unsigned long long)key);
+    }
+  });
+  __syncthreads();
+  int E;
+  if (const int32_t st = gap_groups<false>(S, P, D, tmp, votes, E); st != kOk) return st;
+  gap_sums_per_group(S, E, [&](auto f) __attribute__((always_inline)) {
+    gap_peaks<true>(v, p0, p1, [&](int64_t, double m, double it) { f(m, it, S.cnt[slot_of(m)]); });
+  });
+  return gap_emit<false, uint32_t, true>(S, P, c, n, N, p0, E, 0, 0, 0, out, tmp, red, votes);
+}
+
 // The giant's m/z extent as gap_body's pass 1 leaves it (lo, hi, imax; kb, nw)
 struct GiantExtent {
   double lo, hi, imax;
@@ -1502,6 +1772,11 @@ __device__ __forceinline__ GiantExtent giant_extent(const GapGiant& H, const Gap
   X.lo = f64_from_order_key(~H.lo_inv);
   X.hi = f64_from_order_key(H.hi_key);
   X.imax = f64_from_order_key(H.imax_key);
+  if (!gap_mz_indexable(X.lo, X.hi, P)) {  // no bucket index: every user defers it (nw > wcap)
+    X.kb = 0;
+    X.nw = INT64_MAX;
+    return X;
+  }
   X.kb = floor_div_exact(X.lo, P.bucket_w, P.inv_bucket_w);
   X.nw = (floor_div_exact(X.hi, P.bucket_w, P.inv_bucket_w) - X.kb) / 64 + 1;
   return X;
@@ -1720,7 +1995,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gap_giant_tiles_kernel(GiantArgs A) 
           frexp(fmax(fabs(X.lo), fabs(X.hi)) * (double)N, &ex_m);
           frexp(X.imax * (double)N, &ex_i);
           sc_m = 61 - ex_m;
-          sc_i = 61 - ex_i;
+          sc_i = X.imax == 0.0 ? kGapZeroScale : 61 - ex_i;  // (step 6 reads the sums at the same scale)
           nfg = H.nf != 0;
           Mg = H.M;
           // few groups: this workgroup's sums and counts in LDS first, one global add
@@ -2116,12 +2391,27 @@ __global__ __launch_bounds__(GA_BLOCK) void gap_giant_step_kernel(GiantArgs A, P
       if (H.bad) {  // NaN / inf: one workgroup runs the whole giant in its slice
         st = gap_body_nf(A.v, A.P, S, c, out, tmp, red, votes, reinterpret_cast<uint32_t*>(stage));
         __syncthreads();
+      } else if (st == kOk && H.gany && H.coarse) {  // uniform
+        // the tiled sums' one scale is too coarse (step 6b): the whole giant again in this
+        // workgroup, as the global kernel runs a cluster -- gap_emit hands gap_body to
+        // gap_sums_per_group, and what it writes replaces the flat emit's output
+        st = gap_body<GA_UM, false>(A.v, A.P, S, c, out, tmp, red, votes);
+        if (st == kNonFinite) {
+          __syncthreads();
+          st = gap_body_nf(A.v, A.P, S, c, out, tmp, red, votes, reinterpret_cast<uint32_t*>(stage));
+        }
+        __syncthreads();
       } else if (st == kOk) {
         // the groups were emitted by gap_giant_groups_kernel<4..7>
         (void)n;
         (void)N;
         (void)p0;
         st = H.gany ? kOk : kEmpty;
+      }
+      if (st == kDeferred) {  // a few far m/z outliers past the bitmap's reach?
+        __syncthreads();
+        st = gap_body_far(A.v, A.P, S, c, out, tmp, red, votes);
+        __syncthreads();
       }
       if (st == kDeferred) {
         if (tid == 0) { status[c] = kDeferred; atomicAdd(unresolved, 1); }
@@ -2259,7 +2549,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gap_giant_groups_kernel(GiantArgs A)
         int ex_m, ex_i;
         frexp(fmax(fabs(X.lo), fabs(X.hi)) * (double)N, &ex_m);
         frexp(X.imax * (double)N, &ex_i);
-        const int sc_m = 61 - ex_m, sc_i = 61 - ex_i;
+        const int sc_m = 61 - ex_m, sc_i = X.imax == 0.0 ? kGapZeroScale : 61 - ex_i;
         const double min_len = A.P.min_fraction * (double)n;
         const int E = H.E;
         auto isum = [&](int e) -> double { return ldexp((double)(int64_t)S.kmax[e], -sc_i); };
@@ -2347,6 +2637,20 @@ __global__ __launch_bounds__(GA_BLOCK) void gap_giant_groups_kernel(GiantArgs A)
         int tot;
         const int ex = block_exclusive_scan<GA_BLOCK, int>(mine, tmp, tot);
         if constexpr (PART == 5) {  // (6b) kept groups per chunk
+          // gap_emit's test of the one scale per cluster, over this chunk's groups (a NaN
+          // threshold flags nothing): step 6 sums a flagged giant again, one scale per group
+          const double thr_n = thr * (double)n, thr_lo = thr_n - fabs(thr_n) * 0x1p-30;
+          const double hq_i = ldexp(0.5, -sc_i);
+          int coarse = gap_mz_coarse(X.lo, X.hi, sc_m);
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            const int e = db + q;
+            if (e < E && (double)S.gcnt[e] >= min_len) {
+              const double si = isum(e), err = (double)S.gcnt[e] * hq_i;
+              coarse |= si + err >= thr_lo && err > kGapTol * fabs(si);
+            }
+          }
+          if (__ballot(coarse) != 0ull && lane_id() == 0) atomicOr(&H.coarse, 1);
           if (tid == 0) ch[k] = tot;
         } else {  // (6d) the kept groups in order
           int o = ch[k] + ex;
@@ -2473,6 +2777,10 @@ __global__ __launch_bounds__(GA_BLOCK) void gap_average_global_kernel(CsrView v,
     if (st == kNonFinite) {
       __syncthreads();
       st = gap_body_nf(v, P, S, c, out, tmp, red, votes, reinterpret_cast<uint32_t*>(stage));
+    }
+    if (st == kDeferred) {  // a few far m/z outliers past the bitmap's reach?
+      __syncthreads();
+      st = gap_body_far(v, P, S, c, out, tmp, red, votes);
     }
     if (st == kDeferred) {
       // bucket range beyond the scratch, or a bucket spanning >= mz_accuracy:
