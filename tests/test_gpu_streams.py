@@ -1,7 +1,7 @@
-"""The library-owned side stream (round 6, `SideStream` in csrc/spx_api.hip): spx_bin_mean and
-spx_gap_average fork their large clusters' kernels onto it and join it back to the caller's
-stream.  Two host threads, each with its own batch and its own HIP stream, call both entry
-points over and over at the same time: every call must give the bits a lone call gives (the
+"""The library-owned side stream (round 6, `SideStream` in csrc/spx_api.hip): spx_bin_mean,
+spx_gap_average and spx_medoid fork their large clusters' kernels onto it and join it back to the
+caller's stream.  Two host threads, each with its own batch and its own HIP stream, call all three
+entry points over and over at the same time: every call must give the bits a lone call gives (the
 fork/join events are shared per device, so their enqueue must pair up under the lock), and
 the caller's stream alone must order the results (they are read after synchronising only
 that stream).  (Its first run found a host-side race instead: the packed readback's pinned
@@ -30,14 +30,23 @@ def _digest(res):
     return [np.asarray(h[k]).tobytes() for k in ("out_off", "out_mz", "out_int", "status", "prec")]
 
 
+def _medoid_digest(res):
+    rep, totals = res.to_host()
+    return [rep.tobytes(), totals.tobytes()]
+
+
 def test_side_stream_concurrent_callers(gpu):
     csrs = [_batch_with_giants(101), _batch_with_giants(102)]
     N = np.diff(csrs[0].spec_off[csrs[0].cluster_off])
     assert (N > 65536).any() and ((N > 32768) & (N <= 65536)).any() and (np.diff(csrs[0].cluster_off) > 128).any()
     batches = [engine.DeviceBatch.from_host(c) for c in csrs]
     want = [(_digest(engine.bin_mean(b)), _digest(engine.gap_average(b))) for b in batches]
+    # the third user of the side stream: clusters past MD_NMAX = 64 spectra take medoid's intake
+    assert all(engine.medoid_needs_large_path(b) for b in batches)
+    want_md = [_medoid_digest(engine.medoid(b, with_totals=True)) for b in batches]
     torch.cuda.synchronize()
     got = [[], []]
+    got_md = [[], []]
     errors = []
 
     def worker(i):
@@ -49,8 +58,10 @@ def test_side_stream_concurrent_callers(gpu):
                 for _ in range(4):
                     engine.bin_mean(batches[i], out=bm, stream=s)
                     engine.gap_average(batches[i], out=ga, stream=s)
+                    md = engine.medoid(batches[i], with_totals=True, stream=s)
                     s.synchronize()  # this stream only
                     got[i].append((_digest(bm), _digest(ga)))
+                    got_md[i].append(_medoid_digest(md))
         except Exception as e:  # noqa: BLE001 - reported below
             errors.append(e)
 
@@ -64,3 +75,6 @@ def test_side_stream_concurrent_callers(gpu):
         assert len(got[i]) == 4
         for g in got[i]:
             assert g == want[i]
+        assert len(got_md[i]) == 4
+        for g in got_md[i]:
+            assert g == want_md[i]

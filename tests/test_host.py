@@ -39,6 +39,12 @@ def test_hip_library_exports_every_declared_symbol():
     assert not missing, missing
     L.spx_abi_version.restype = ctypes.c_int
     assert L.spx_abi_version() == _lib.SPX_ABI_VERSION == 2
+    # and no spx_* name exported that the header leaves out
+    # (nm is part of binutils, which the build already needs: its absence is a failure, not a skip)
+    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True)
+    assert nm.returncode == 0, nm.stderr
+    exported = sorted(set(re.findall(r"\b[TW] (spx_[a-z0-9_]+)$", nm.stdout, flags=re.M)))
+    assert exported == sorted(_lib.EXPORTED)
 
 
 MGF_HEADER = os.path.join(REPO, "include", "spx_mgf.h")
