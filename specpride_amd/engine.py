@@ -435,6 +435,14 @@ def medoid_needs_large_path(batch: DeviceBatch) -> bool:
     return v
 
 
+def _medoid_large(batch: DeviceBatch, tolerance) -> bool:
+    """The large path is on for this batch at this tolerance: a cluster is large by size,
+    or a checked call saw one deferred at run time (its bins past the LDS tables) and
+    remembered it -- without the large path such a cluster stays REP_DEFERRED, so the
+    unchecked calls that follow a checked one must keep it on."""
+    return medoid_needs_large_path(batch) or bool(batch._ws.get(("medoid_late", float(tolerance))))
+
+
 def medoid(batch: DeviceBatch, tolerance=0.1, with_totals=False, out: Optional[MedoidResult] = None,
            stream=None, check: bool = True) -> MedoidResult:
     """distance() + the medoid loop (most_similar_representative.py:13-111) for every cluster.
@@ -444,14 +452,15 @@ def medoid(batch: DeviceBatch, tolerance=0.1, with_totals=False, out: Optional[M
     for the result and, if a cluster was deferred at run time (REP_DEFERRED) or
     ran out of arena (REP_ARENA), re-runs with the large path on and those clusters
     budgeted in the arena, so every cluster comes back resolved or REP_RANGE.
-    ``check=False`` only enqueues (timed loops that were checked once)."""
+    ``check=False`` only enqueues (timed loops that were checked once: the batch remembers
+    what the checked call learned, so the unchecked ones give the same results)."""
     import torch
 
     if out is None:
         out = MedoidResult(torch.empty(max(batch.n_clusters, 1), dtype=torch.int64, device=batch.device),
                            torch.empty(max(batch.n_spectra, 1), dtype=torch.float64, device=batch.device)
                            if with_totals else None)
-    large = medoid_needs_large_path(batch)
+    large = _medoid_large(batch, tolerance)
     extra = batch._ws.get("medoid_extra", ())
     _medoid_launch(batch, tolerance, large or bool(extra), out, extra, stream)
     if not check or batch.n_clusters == 0:
@@ -461,6 +470,7 @@ def medoid(batch: DeviceBatch, tolerance=0.1, with_totals=False, out: Optional[M
         bad = torch.nonzero((rep == REP_DEFERRED) | (rep == REP_ARENA)).flatten().cpu().numpy()
         if len(bad) == 0:
             break
+        batch._ws[("medoid_late", float(tolerance))] = True  # later unchecked calls: the large path stays on
         arena = np.flatnonzero(out.rep[:batch.n_clusters].cpu().numpy() == REP_ARENA)
         extra = tuple(sorted(set(extra) | set(int(c) for c in arena)))
         batch._ws["medoid_extra"] = extra
@@ -470,11 +480,12 @@ def medoid(batch: DeviceBatch, tolerance=0.1, with_totals=False, out: Optional[M
 
 def bin_mean_medoid(batch: DeviceBatch, minimum=100.0, maximum=2000.0, binsize=0.02, apply_peak_quorum=True,
                     tolerance=0.1, out_bm: Optional[PeaksResult] = None, out_md: Optional[MedoidResult] = None,
-                    stream=None, check: bool = True):
+                    stream=None, check: bool = True, with_totals: bool = False):
     """bin_mean() and medoid() of the same batch in one pass (spx_bin_mean_medoid: each
     cluster's two register bodies share one workgroup); results identical to the two
-    calls.  ``check`` as in :func:`medoid` (run-time deferrals re-run by medoid()).
-    Returns (PeaksResult, MedoidResult).
+    calls.  ``check`` as in :func:`medoid` (run-time deferrals re-run by medoid());
+    ``with_totals`` as in :func:`medoid` (ignored when ``out_md`` is passed: its own
+    ``totals`` decide).  Returns (PeaksResult, MedoidResult).
 
     A checked call runs stage 1 of spx_bin_mean_medoid_stage (the fused register pass),
     reads how many clusters each register body handed on, and enqueues stage 2 (both
@@ -495,8 +506,10 @@ def bin_mean_medoid(batch: DeviceBatch, minimum=100.0, maximum=2000.0, binsize=0
     out_bm.stream = stream
     out_bm.pending = None
     if out_md is None:
-        out_md = MedoidResult(torch.empty(max(batch.n_clusters, 1), dtype=torch.int64, device=batch.device), None)
-    large = medoid_needs_large_path(batch)
+        out_md = MedoidResult(torch.empty(max(batch.n_clusters, 1), dtype=torch.int64, device=batch.device),
+                              torch.empty(max(batch.n_spectra, 1), dtype=torch.float64, device=batch.device)
+                              if with_totals else None)
+    large = _medoid_large(batch, tolerance)
     extra = batch._ws.get("medoid_extra", ())
     key = ("medoid_size", tuple(extra))
     need_md = batch._ws.get(key)

@@ -6,7 +6,8 @@ GAP_RTOL).  Each case draws cluster sizes (1..300, heavy tails), spectrum length
 snapped to a coarse grid (several peaks per bin, exact m/z ties), unsorted
 spectra, empty spectra, a mixed-charge cluster, m/z past the medoid's register
 range and bin range, zero intensities, and non-default bin-mean / gap-average
-parameters; the binned cosine, xcorr distance and best score ride along."""
+parameters; the fused bin-mean + medoid pass, the binned cosine, xcorr distance and best
+score ride along."""
 import numpy as np
 import pytest
 
@@ -14,6 +15,7 @@ from oracle import c_oracle, np_oracle
 from specpride_amd import engine
 from specpride_amd.csr import SpectraCSR
 from specpride_amd.synthetic import make_clusters_np
+from test_gpu_fused import _check
 from test_gpu_parity import assert_bin_mean_equal, assert_gap_close
 
 pytestmark = pytest.mark.gpu
@@ -96,6 +98,18 @@ def test_fuzz_medoid(gpu, seed):
     ref_rep, ref_tot = c_oracle.medoid(csr, tol=tol, with_totals=True)
     np.testing.assert_array_equal(rep, ref_rep)
     np.testing.assert_array_equal(tot, ref_tot)
+
+
+@pytest.mark.parametrize("seed", range(N_CASES))
+def test_fuzz_fused(gpu, seed):
+    """The same batches through spx_bin_mean_medoid (test_gpu_fused._check: the C oracle,
+    the separate entry points, unchecked and reused outputs, totals included): once with
+    the defaults, once with the case's other bin parameters and test_fuzz_medoid's other
+    tolerance."""
+    csr, params = _case(seed)
+    _check(csr, params[0], 0.1)
+    tol = float(np.random.default_rng(4000 + seed).choice([0.02, 0.05, 0.3, 1.0]))
+    _check(csr, params[1], tol)
 
 
 @pytest.mark.parametrize("seed", range(N_CASES))
