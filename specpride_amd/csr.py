@@ -19,6 +19,16 @@ from typing import Iterable, Sequence
 
 import numpy as np
 
+# the layout above as data: (name, dtype) in the order every packed copy uses
+CSR_FIELDS = (("cluster_off", np.int64), ("spec_off", np.int64), ("mz", np.float64), ("inten", np.float64),
+              ("prec_mz", np.float64), ("charge", np.int32), ("rt", np.float64))
+
+
+def csr_lengths(n_clusters: int, n_spectra: int, n_peaks: int) -> dict:
+    """Elements per field of a batch of C clusters, S spectra and P peaks."""
+    C, S, P = n_clusters, n_spectra, n_peaks
+    return dict(cluster_off=C + 1, spec_off=S + 1, mz=P, inten=P, prec_mz=S, charge=S, rt=S)
+
 
 def concat_ranges(starts: np.ndarray, lens: np.ndarray) -> np.ndarray:
     """concatenate(arange(s, s + n) for s, n in zip(starts, lens)), vectorised."""
@@ -45,13 +55,8 @@ class SpectraCSR:
     titles: list = field(default_factory=list)
 
     def __post_init__(self):
-        self.cluster_off = np.ascontiguousarray(self.cluster_off, np.int64)
-        self.spec_off = np.ascontiguousarray(self.spec_off, np.int64)
-        self.mz = np.ascontiguousarray(self.mz, np.float64)
-        self.inten = np.ascontiguousarray(self.inten, np.float64)
-        self.prec_mz = np.ascontiguousarray(self.prec_mz, np.float64)
-        self.charge = np.ascontiguousarray(self.charge, np.int32)
-        self.rt = np.ascontiguousarray(self.rt, np.float64)
+        for name, dt in CSR_FIELDS:
+            setattr(self, name, np.ascontiguousarray(getattr(self, name), dt))
         self.validate()
 
     # ------------------------------------------------------------------ shape

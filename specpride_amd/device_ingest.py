@@ -80,7 +80,7 @@ def _h2d(a, dev, stream):
     import torch
 
     a = np.ascontiguousarray(a)
-    t = torch.empty(a.shape, dtype=getattr(torch, engine._TORCH_DT[a.dtype]), device=dev)
+    t = torch.empty(a.shape, dtype=engine.dtype_of(a.dtype), device=dev)
     _lib.check(_lib.lib().spx_copy_h2d(t.data_ptr(), a.ctypes.data, a.nbytes, stream.cuda_stream), "spx_copy_h2d")
     return t
 
@@ -258,7 +258,7 @@ def load(path, general: bool, group_mode: int, device="cuda", stages=None):
                        mz=got["mz"][:n_peaks], inten=got["inten"][:n_peaks], prec_mz=got["prec_mz"][:n_used],
                        charge=got["charge"][:n_used], rt=got["rt"][:n_used], n_clusters=len(sizes),
                        n_spectra=n_used, n_peaks=n_peaks)
-        batch = engine.DeviceBatch(tensors, cluster_off, host_spec_off, engine._device_span(tensors["mz"]),
+        batch = engine.DeviceBatch(tensors, cluster_off, host_spec_off, engine.device_span(tensors["mz"]),
                                    cluster_ids=ids)
     f = flags[:n_used]
     meta = Meta(ids=ids, sizes=sizes, records=order[:n_used], flags=f, has_prec=(f & 1) != 0,

@@ -20,7 +20,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .csr import SpectraCSR
+from .csr import CSR_FIELDS, SpectraCSR
 
 STATUS_OK, STATUS_MIXED_CHARGE, STATUS_NO_GAP, STATUS_EMPTY, STATUS_NON_FINITE = 0, 1, 2, 3, 4
 STATUS_UNRESOLVED = 100
@@ -66,13 +66,26 @@ class _Pinned(threading.local):
 _H2D, _D2H = _Pinned(), _Pinned()
 
 
-def _layout(items):
-    """Byte offsets (256-aligned) of (name, numpy array) items; total bytes."""
+def aligned_layout(sizes):
+    """Byte offsets (256-aligned) of (name, byte size) pairs; total bytes."""
     off, o = {}, 0
-    for name, a in items:
+    for name, nbytes in sizes:
         off[name] = o
-        o += (a.nbytes + 255) & ~255
+        o += (nbytes + 255) & ~255
     return off, o
+
+
+_DTYPES = {}  # numpy dtype <-> torch dtype of the ABI's element types, filled on first use
+
+
+def dtype_of(dt):
+    """The torch dtype of a numpy dtype, or the numpy dtype of a torch dtype."""
+    if not _DTYPES:
+        import torch
+
+        pairs = [(np.dtype(n), getattr(torch, n)) for n in ("int64", "float64", "int32")]
+        _DTYPES.update(pairs + [(t, n) for n, t in pairs])
+    return _DTYPES[dt]
 
 
 class DeviceBatch:
@@ -102,14 +115,13 @@ class DeviceBatch:
 
     @classmethod
     def from_host(cls, csr: SpectraCSR, device="cuda") -> "DeviceBatch":
-        items = [("cluster_off", csr.cluster_off), ("spec_off", csr.spec_off), ("mz", csr.mz),
-                 ("inten", csr.inten), ("prec_mz", csr.prec_mz), ("charge", csr.charge), ("rt", csr.rt)]
-        off, total = _layout(items)
+        items = [(name, getattr(csr, name)) for name, _ in CSR_FIELDS]
+        off, total = aligned_layout((name, a.nbytes) for name, a in items)
         if total > PACKED_MAX_BYTES:
             # large batches: the span is reduced in HBM after the copy (a host
             # pass over the m/z array costs more than its transfer)
             tensors = _staged_to_device(items, off, total, device)
-            span = _device_span(tensors["mz"])
+            span = device_span(tensors["mz"])
         else:
             # the m/z span over FINITE values only: a NaN/inf peak makes its cluster
             # SPX_NON_FINITE, it must not blow up the workspace sizing of the others
@@ -122,10 +134,8 @@ class DeviceBatch:
     @classmethod
     def from_device(cls, tensors: dict) -> "DeviceBatch":
         """Wrap tensors already in HBM (e.g. synthetic.make_clusters_torch)."""
-        import torch
-
         return cls(tensors, tensors["cluster_off"].cpu().numpy(), tensors["spec_off"].cpu().numpy(),
-                   _device_span(tensors["mz"]))
+                   device_span(tensors["mz"]))
 
     def workspace(self, key: str, nbytes: int):
         import torch
@@ -142,7 +152,7 @@ class DeviceBatch:
         return self.t["mz"].device
 
 
-def _device_span(mz) -> float:
+def device_span(mz) -> float:
     """max - min over the finite values of a device m/z tensor (0.0 if none)."""
     import torch
 
@@ -171,14 +181,8 @@ def _packed_to_device(items, off, total, device):
     return _views(dev, items, off)
 
 
-_TORCH_DT = {np.dtype(np.int64): "int64", np.dtype(np.float64): "float64", np.dtype(np.int32): "int32"}
-
-
 def _views(dev, items, off):
-    import torch
-
-    return {name: dev[off[name]:off[name] + a.nbytes].view(getattr(torch, _TORCH_DT[a.dtype]))
-            for name, a in items}
+    return {name: dev[off[name]:off[name] + a.nbytes].view(dtype_of(a.dtype)) for name, a in items}
 
 
 def _staged_to_device(items, off, total, device):
@@ -209,8 +213,7 @@ def to_host_array(t) -> np.ndarray:
     if n <= PACKED_MAX_BYTES or t.device.type != "cuda":
         return t.cpu().numpy()
     t = t.contiguous()
-    np_dt = {torch.int64: np.int64, torch.float64: np.float64, torch.int32: np.int32}[t.dtype]
-    out = np.empty(t.numel(), np_dt)
+    out = np.empty(t.numel(), dtype_of(t.dtype))
     with torch.cuda.device(t.device):
         _lib.check(_lib.lib().spx_copy_d2h(out.ctypes.data, t.data_ptr(), n,
                                            torch.cuda.current_stream(t.device).cuda_stream), "spx_copy_d2h")
@@ -233,8 +236,7 @@ def _packed_to_host(tensors):
     res, o = {}, 0
     for name, t in tensors:
         nb = t.numel() * t.element_size()
-        np_dt = {torch.int64: np.int64, torch.float64: np.float64, torch.int32: np.int32}[t.dtype]
-        res[name] = hv[o:o + nb].view(np_dt).copy()
+        res[name] = hv[o:o + nb].view(dtype_of(t.dtype)).copy()
         o += nb
     return res
 
@@ -299,10 +301,15 @@ class PeaksResult:
         out_off, mz, inten = self.compact()
         if self.stream is not None:  # the readback copies run on the batch device's current stream
             torch.cuda.current_stream(self.batch.device).wait_stream(self.stream)
-        d = dict(out_off=out_off.cpu().numpy(), out_mz=to_host_array(mz), out_int=to_host_array(inten),
-                 status=self.status.cpu().numpy(), prec=self.prec.cpu().numpy(), charge=self.charge.cpu().numpy())
+        return self._result(out_off.cpu().numpy(), to_host_array(mz), to_host_array(inten),
+                            lambda k: getattr(self, k).cpu().numpy())
+
+    def _result(self, out_off, out_mz, out_int, scalar) -> dict:
+        """The dict to_host() returns; ``scalar(name)`` is the host copy of a per-cluster field."""
+        d = dict(out_off=out_off, out_mz=out_mz, out_int=out_int, status=scalar("status"), prec=scalar("prec"),
+                 charge=scalar("charge"))
         if self.rt is not None:
-            d["rt"] = self.rt.cpu().numpy()
+            d["rt"] = scalar("rt")
         return d
 
     def _to_host_small(self) -> dict:
@@ -323,21 +330,35 @@ class PeaksResult:
         np.cumsum(count, out=out_off[1:])
         base = self.batch.host_spec_off[self.batch.host_cluster_off[:C]]
         idx = np.repeat(base - out_off[:-1], count) + np.arange(out_off[-1], dtype=np.int64)
-        d = dict(out_off=out_off, out_mz=h["mz"][idx], out_int=h["inten"][idx], status=h["status"],
-                 prec=h["prec"], charge=h["charge"])
-        if self.rt is not None:
-            d["rt"] = h["rt"]
-        return d
+        return self._result(out_off, h["mz"][idx], h["inten"][idx], h.__getitem__)
 
 
-def _alloc_peaks(batch: DeviceBatch):
+def alloc_peaks(device, n_peaks: int, n_clusters: int, rt: bool = False, batch=None) -> PeaksResult:
+    """A new PeaksResult with room for ``n_peaks`` peaks and ``n_clusters`` clusters
+    (count, status and charge zeroed, the rest uninitialised)."""
     import torch
 
-    dev = batch.device
-    P, C = max(batch.n_peaks, 1), max(batch.n_clusters, 1)
-    return (torch.empty(P, dtype=torch.float64, device=dev), torch.empty(P, dtype=torch.float64, device=dev),
-            torch.zeros(C, dtype=torch.int64, device=dev), torch.zeros(C, dtype=torch.int32, device=dev),
-            torch.empty(C, dtype=torch.float64, device=dev), torch.zeros(C, dtype=torch.int32, device=dev))
+    P, C = max(n_peaks, 1), max(n_clusters, 1)
+    f64 = lambda n: torch.empty(n, dtype=torch.float64, device=device)  # noqa: E731
+    zeros = lambda dt: torch.zeros(C, dtype=dt, device=device)  # noqa: E731
+    return PeaksResult(batch, f64(P), f64(P), zeros(torch.int64), zeros(torch.int32), f64(C), zeros(torch.int32),
+                       rt=f64(C) if rt else None)
+
+
+def _peaks_out(batch: DeviceBatch, out: Optional[PeaksResult], stream, rt: bool = False) -> PeaksResult:
+    """``out``, or a new result of the batch's own size, marked as produced on ``stream``."""
+    if out is None:
+        out = alloc_peaks(batch.device, batch.n_peaks, batch.n_clusters, rt, batch)
+    out.stream = stream
+    return out
+
+
+def _bin_setup(batch: DeviceBatch, minimum, maximum, binsize, apply_peak_quorum):
+    """(SpxBinParams, bin-mean workspace) of a bin_mean / bin_mean_medoid call."""
+    prm = _lib.SpxBinParams(float(minimum), float(maximum), float(binsize), int(apply_peak_quorum is True))
+    L = _lib.lib()
+    need = L.spx_bin_mean_workspace_size(ctypes.byref(batch.csr), ctypes.byref(prm), ctypes.byref(batch.info))
+    return prm, batch.workspace("bin_mean", need)
 
 
 def bin_mean(batch: DeviceBatch, minimum=100.0, maximum=2000.0, binsize=0.02, apply_peak_quorum=True,
@@ -350,13 +371,8 @@ def bin_mean(batch: DeviceBatch, minimum=100.0, maximum=2000.0, binsize=0.02, ap
     shims): 17 fewer empty launches per call.  Device-side consumers of the result
     must not use it."""
     L = _lib.lib()
-    prm = _lib.SpxBinParams(float(minimum), float(maximum), float(binsize), int(apply_peak_quorum is True))
-    need = L.spx_bin_mean_workspace_size(ctypes.byref(batch.csr), ctypes.byref(prm), ctypes.byref(batch.info))
-    ws = batch.workspace("bin_mean", need)
-    if out is None:
-        mz, it, cnt, st, prec, ch = _alloc_peaks(batch)
-        out = PeaksResult(batch, mz, it, cnt, st, prec, ch)
-    out.stream = stream
+    prm, ws = _bin_setup(batch, minimum, maximum, binsize, apply_peak_quorum)
+    out = _peaks_out(batch, out, stream)
     po = _lib.SpxPeaksOut(_ptr(out.mz), _ptr(out.inten), _ptr(out.count))
 
     def launch(stage):
@@ -373,8 +389,6 @@ def gap_average(batch: DeviceBatch, mz_accuracy=0.01, dyn_range=1000.0, min_frac
                 pepmass="lower_median", rt="mass_lower_median", proton=PROTON,
                 out: Optional[PeaksResult] = None, stream=None) -> PeaksResult:
     """average_spectrum (average_spectrum_clustering.py:26-103) + precursor helpers for every cluster."""
-    import torch
-
     L = _lib.lib()
     if batch.t.get("rt") is None:
         raise ValueError("gap_average needs per-spectrum RT (NaN where absent)")
@@ -382,11 +396,7 @@ def gap_average(batch: DeviceBatch, mz_accuracy=0.01, dyn_range=1000.0, min_frac
                             PEPMASS_MODES[pepmass], RT_MODES[rt])
     need = L.spx_gap_average_workspace_size(ctypes.byref(batch.csr), ctypes.byref(prm), ctypes.byref(batch.info))
     ws = batch.workspace("gap_average", need)
-    if out is None:
-        mz, it, cnt, st, prec, ch = _alloc_peaks(batch)
-        out = PeaksResult(batch, mz, it, cnt, st, prec, ch,
-                          rt=torch.empty(max(batch.n_clusters, 1), dtype=torch.float64, device=batch.device))
-    out.stream = stream
+    out = _peaks_out(batch, out, stream, rt=True)
     po = _lib.SpxPeaksOut(_ptr(out.mz), _ptr(out.inten), _ptr(out.count))
     _lib.check(L.spx_gap_average(ctypes.byref(batch.csr), ctypes.byref(prm), ctypes.byref(batch.info),
                                  ctypes.byref(po), _ptr(out.prec), _ptr(out.charge), _ptr(out.rt), _ptr(out.status),
@@ -406,22 +416,98 @@ class MedoidResult:
         return self.rep.cpu().numpy(), (None if self.totals is None else self.totals.cpu().numpy())
 
 
-def _medoid_launch(batch: DeviceBatch, tolerance, large_path: bool, out: MedoidResult, extra, stream):
-    L = _lib.lib()
-    key = ("medoid_size", tuple(extra))
-    need = batch._ws.get(key)
+def alloc_medoid(device, n_clusters: int, n_spectra: int = 0, totals: bool = False) -> MedoidResult:
+    """A new MedoidResult for ``n_clusters`` clusters (``totals``: of ``n_spectra`` spectra), uninitialised."""
+    import torch
+
+    return MedoidResult(torch.empty(max(n_clusters, 1), dtype=torch.int64, device=device),
+                        torch.empty(max(n_spectra, 1), dtype=torch.float64, device=device) if totals else None)
+
+
+# What a batch remembers about its medoid calls lives in ``batch._ws`` under "medoid_needs_large"
+# (a cluster is large by size), ("medoid_late", tol) (a checked call at tol met a deferral),
+# "medoid_extra" (cluster ids budgeted in the arena), ("medoid_size", extra) (workspace bytes)
+# and ("fused_clean", ...).  The rules that read and write them follow; they take the dict
+# and host arrays only (no device, no library), so tests/test_engine_policy.py runs them.
+def medoid_mode(ws: dict, needs_large: bool, tolerance):
+    """(large_path, extra) of a medoid launch at ``tolerance``.  The large path is on when a
+    cluster is large by size, or a checked call met a run-time deferral at this tolerance or
+    budgeted clusters in the arena: without it such a cluster stays REP_DEFERRED."""
+    extra = ws.get("medoid_extra", ())
+    return bool(needs_large or ws.get(("medoid_late", float(tolerance))) or extra), extra
+
+
+def medoid_unresolved(rep) -> bool:
+    """Host ``rep`` codes hold a run-time deferral (REP_DEFERRED: bins past the LDS tables,
+    REP_ARENA: out of arena), which a checked call resolves; the other codes are final."""
+    return bool(np.any((rep == REP_DEFERRED) | (rep == REP_ARENA)))
+
+
+def medoid_learn(ws: dict, tolerance, rep) -> bool:
+    """Record what the host ``rep`` codes of one call show: the large path stays on at this
+    tolerance and the REP_ARENA clusters are budgeted.  True if the call must be re-run."""
+    if not medoid_unresolved(rep):
+        return False
+    ws[("medoid_late", float(tolerance))] = True
+    arena = np.flatnonzero(rep == REP_ARENA)
+    ws["medoid_extra"] = tuple(sorted(set(ws.get("medoid_extra", ())) | set(int(c) for c in arena)))
+    return True
+
+
+def medoid_resolve(ws: dict, tolerance, read_codes, launch) -> None:
+    """After a launch: read the host codes, learn from them and, while a cluster is
+    unresolved, ``launch()`` again under what was learned (twice at the most)."""
+    for _ in range(2):
+        if not medoid_learn(ws, tolerance, read_codes()):
+            break
+        launch()
+
+
+def fused_key(prm, mprm) -> tuple:
+    """Key of the fused pass's remembered finding; large_path is in it, so a learned deferral forgets it."""
+    return ("fused_clean", prm.minimum, prm.maximum, prm.binsize, prm.apply_peak_quorum, mprm.tolerance,
+            mprm.large_path)
+
+
+def fused_stage(ws: dict, key: tuple, clean: Optional[bool] = None) -> int:
+    """The stage of an unchecked bin_mean_medoid call: 1 (the fused register pass alone) if a checked
+    call found that it hands no cluster on (``clean``, stored first when given), else 0 (all)."""
+    if clean is not None:
+        ws[key] = bool(clean)
+    return 1 if ws.get(key) else 0
+
+
+def _medoid_setup(batch: DeviceBatch, tolerance):
+    """(SpxMedoidParams, workspace) of a medoid launch under what the batch remembers."""
+    large, extra = medoid_mode(batch._ws, medoid_needs_large_path(batch), tolerance)
+    need = batch._ws.get(("medoid_size", extra))
     if need is None:
-        ex = np.ascontiguousarray(extra, np.int64)
-        need = L.spx_medoid_workspace_size(batch.host_cluster_off.ctypes.data_as(ctypes.c_void_p),
-                                           batch.host_spec_off.ctypes.data_as(ctypes.c_void_p), batch.n_clusters,
-                                           ex.ctypes.data_as(ctypes.c_void_p) if len(ex) else None, len(ex))
+        ex, vp = np.ascontiguousarray(extra, np.int64), ctypes.c_void_p
+        need = _lib.lib().spx_medoid_workspace_size(batch.host_cluster_off.ctypes.data_as(vp),
+                                                    batch.host_spec_off.ctypes.data_as(vp), batch.n_clusters,
+                                                    ex.ctypes.data_as(vp) if len(ex) else None, len(ex))
         if need == 0:
             raise ValueError("spx_medoid_workspace_size: invalid offsets")
-        batch._ws[key] = need
-    ws = batch.workspace("medoid", need)
-    prm = _lib.SpxMedoidParams(float(tolerance), int(bool(large_path)))
-    _lib.check(L.spx_medoid(ctypes.byref(batch.csr), ctypes.byref(prm), _ptr(out.rep), _ptr(out.totals), _ptr(ws),
-                            ws.numel(), _stream_handle(stream)), "spx_medoid")
+        batch._ws[("medoid_size", extra)] = need
+    return _lib.SpxMedoidParams(float(tolerance), int(large)), batch.workspace("medoid", need)
+
+
+def _medoid_launch(batch: DeviceBatch, tolerance, out: MedoidResult, stream) -> None:
+    prm, ws = _medoid_setup(batch, tolerance)
+    _lib.check(_lib.lib().spx_medoid(ctypes.byref(batch.csr), ctypes.byref(prm), _ptr(out.rep), _ptr(out.totals),
+                                     _ptr(ws), ws.numel(), _stream_handle(stream)), "spx_medoid")
+
+
+def _medoid_checked(batch: DeviceBatch, tolerance, out: MedoidResult, stream) -> None:
+    """The checked part of medoid() and bin_mean_medoid(), after their own launch."""
+    import torch
+
+    def read_codes():
+        if stream is not None:  # the copy runs on the current stream: order it after the producer
+            torch.cuda.current_stream(batch.device).wait_stream(stream)
+        return out.rep[:batch.n_clusters].cpu().numpy()
+
+    medoid_resolve(batch._ws, tolerance, read_codes, lambda: _medoid_launch(batch, tolerance, out, stream))
 
 
 def medoid_needs_large_path(batch: DeviceBatch) -> bool:
@@ -435,14 +521,6 @@ def medoid_needs_large_path(batch: DeviceBatch) -> bool:
     return v
 
 
-def _medoid_large(batch: DeviceBatch, tolerance) -> bool:
-    """The large path is on for this batch at this tolerance: a cluster is large by size,
-    or a checked call saw one deferred at run time (its bins past the LDS tables) and
-    remembered it -- without the large path such a cluster stays REP_DEFERRED, so the
-    unchecked calls that follow a checked one must keep it on."""
-    return medoid_needs_large_path(batch) or bool(batch._ws.get(("medoid_late", float(tolerance))))
-
-
 def medoid(batch: DeviceBatch, tolerance=0.1, with_totals=False, out: Optional[MedoidResult] = None,
            stream=None, check: bool = True) -> MedoidResult:
     """distance() + the medoid loop (most_similar_representative.py:13-111) for every cluster.
@@ -454,27 +532,11 @@ def medoid(batch: DeviceBatch, tolerance=0.1, with_totals=False, out: Optional[M
     budgeted in the arena, so every cluster comes back resolved or REP_RANGE.
     ``check=False`` only enqueues (timed loops that were checked once: the batch remembers
     what the checked call learned, so the unchecked ones give the same results)."""
-    import torch
-
     if out is None:
-        out = MedoidResult(torch.empty(max(batch.n_clusters, 1), dtype=torch.int64, device=batch.device),
-                           torch.empty(max(batch.n_spectra, 1), dtype=torch.float64, device=batch.device)
-                           if with_totals else None)
-    large = _medoid_large(batch, tolerance)
-    extra = batch._ws.get("medoid_extra", ())
-    _medoid_launch(batch, tolerance, large or bool(extra), out, extra, stream)
-    if not check or batch.n_clusters == 0:
-        return out
-    for _ in range(2):
-        rep = out.rep[:batch.n_clusters]
-        bad = torch.nonzero((rep == REP_DEFERRED) | (rep == REP_ARENA)).flatten().cpu().numpy()
-        if len(bad) == 0:
-            break
-        batch._ws[("medoid_late", float(tolerance))] = True  # later unchecked calls: the large path stays on
-        arena = np.flatnonzero(out.rep[:batch.n_clusters].cpu().numpy() == REP_ARENA)
-        extra = tuple(sorted(set(extra) | set(int(c) for c in arena)))
-        batch._ws["medoid_extra"] = extra
-        _medoid_launch(batch, tolerance, True, out, extra, stream)
+        out = alloc_medoid(batch.device, batch.n_clusters, batch.n_spectra, with_totals)
+    _medoid_launch(batch, tolerance, out, stream)
+    if check and batch.n_clusters:
+        _medoid_checked(batch, tolerance, out, stream)
     return out
 
 
@@ -483,7 +545,7 @@ def bin_mean_medoid(batch: DeviceBatch, minimum=100.0, maximum=2000.0, binsize=0
                     stream=None, check: bool = True, with_totals: bool = False):
     """bin_mean() and medoid() of the same batch in one pass (spx_bin_mean_medoid: each
     cluster's two register bodies share one workgroup); results identical to the two
-    calls.  ``check`` as in :func:`medoid` (run-time deferrals re-run by medoid());
+    calls.  ``check`` as in :func:`medoid` (run-time deferrals re-run by spx_medoid);
     ``with_totals`` as in :func:`medoid` (ignored when ``out_md`` is passed: its own
     ``totals`` decide).  Returns (PeaksResult, MedoidResult).
 
@@ -497,32 +559,12 @@ def bin_mean_medoid(batch: DeviceBatch, minimum=100.0, maximum=2000.0, binsize=0
     import torch
 
     L = _lib.lib()
-    prm = _lib.SpxBinParams(float(minimum), float(maximum), float(binsize), int(apply_peak_quorum is True))
-    need = L.spx_bin_mean_workspace_size(ctypes.byref(batch.csr), ctypes.byref(prm), ctypes.byref(batch.info))
-    ws_bm = batch.workspace("bin_mean", need)
-    if out_bm is None:
-        mz, it, cnt, st, prec, ch = _alloc_peaks(batch)
-        out_bm = PeaksResult(batch, mz, it, cnt, st, prec, ch)
-    out_bm.stream = stream
+    prm, ws_bm = _bin_setup(batch, minimum, maximum, binsize, apply_peak_quorum)
+    out_bm = _peaks_out(batch, out_bm, stream)
     out_bm.pending = None
     if out_md is None:
-        out_md = MedoidResult(torch.empty(max(batch.n_clusters, 1), dtype=torch.int64, device=batch.device),
-                              torch.empty(max(batch.n_spectra, 1), dtype=torch.float64, device=batch.device)
-                              if with_totals else None)
-    large = _medoid_large(batch, tolerance)
-    extra = batch._ws.get("medoid_extra", ())
-    key = ("medoid_size", tuple(extra))
-    need_md = batch._ws.get(key)
-    if need_md is None:
-        ex = np.ascontiguousarray(extra, np.int64)
-        need_md = L.spx_medoid_workspace_size(batch.host_cluster_off.ctypes.data_as(ctypes.c_void_p),
-                                              batch.host_spec_off.ctypes.data_as(ctypes.c_void_p), batch.n_clusters,
-                                              ex.ctypes.data_as(ctypes.c_void_p) if len(ex) else None, len(ex))
-        if need_md == 0:
-            raise ValueError("spx_medoid_workspace_size: invalid offsets")
-        batch._ws[key] = need_md
-    ws_md = batch.workspace("medoid", need_md)
-    mprm = _lib.SpxMedoidParams(float(tolerance), int(bool(large or extra)))
+        out_md = alloc_medoid(batch.device, batch.n_clusters, batch.n_spectra, with_totals)
+    mprm, ws_md = _medoid_setup(batch, tolerance)
     po = _lib.SpxPeaksOut(_ptr(out_bm.mz), _ptr(out_bm.inten), _ptr(out_bm.count))
 
     def launch(stage, handoff=None):
@@ -532,10 +574,9 @@ def bin_mean_medoid(batch: DeviceBatch, minimum=100.0, maximum=2000.0, binsize=0
                                                _ptr(out_md.rep), _ptr(out_md.totals), _ptr(ws_md), ws_md.numel(),
                                                _stream_handle(stream), stage, _ptr(handoff)), "spx_bin_mean_medoid")
 
-    clean_key = ("fused_clean", prm.minimum, prm.maximum, prm.binsize, prm.apply_peak_quorum, mprm.tolerance,
-                 mprm.large_path)
+    clean_key = fused_key(prm, mprm)
     if not check or not batch.n_clusters:
-        launch(1 if batch._ws.get(clean_key) else 0)
+        launch(fused_stage(batch._ws, clean_key))
         return out_bm, out_md
     hand = batch.workspace("handoff", 8)[:8].view(torch.int32)
     launch(1, hand)
@@ -544,11 +585,8 @@ def bin_mean_medoid(batch: DeviceBatch, minimum=100.0, maximum=2000.0, binsize=0
     n_bm, n_md = (int(x) for x in hand.cpu())
     if n_bm or n_md:
         launch(2)
-    batch._ws[clean_key] = not (n_bm or n_md)
-    if check and batch.n_clusters:
-        rep = out_md.rep[:batch.n_clusters]
-        if bool(((rep == REP_DEFERRED) | (rep == REP_ARENA)).any().item()):
-            medoid(batch, tolerance=tolerance, out=out_md, stream=stream, check=True)
+    fused_stage(batch._ws, clean_key, clean=not (n_bm or n_md))
+    _medoid_checked(batch, tolerance, out_md, stream)
     return out_bm, out_md
 
 

@@ -120,10 +120,16 @@ def representatives(spectra, names):
     return _choose(csr, runs)
 
 
-def _choose(csr, runs):
-    rep, _ = engine.medoid(engine.DeviceBatch.from_host(csr), TOLERANCE).to_host()
+def _medoid_rep(batch):
+    """Host ``rep`` of the batch's medoid; every cluster must have come back resolved."""
+    rep, _ = engine.medoid(batch, TOLERANCE).to_host()
     if np.any(rep < 0):
         raise RuntimeError("medoid engine could not resolve a cluster (see DESIGN.md limits)")
+    return rep
+
+
+def _choose(csr, runs):
+    rep = _medoid_rep(engine.DeviceBatch.from_host(csr))
     out = []
     for c, (cl, members) in enumerate(runs):
         out.append((cl, members, members[int(rep[c] - csr.cluster_off[c])]))
@@ -149,9 +155,7 @@ def _main_native(inputfile, outputfile):
     records = np.flatnonzero(key >= 0)  # each id's first run, runs in file order
     sizes = np.bincount(key[records], minlength=len(ids))
     csr = ingest.csr_from_flat(flat, sizes, None if len(records) == len(key) else records)
-    rep, _ = engine.medoid(engine.DeviceBatch.from_host(csr), TOLERANCE).to_host()
-    if np.any(rep < 0):
-        raise RuntimeError("medoid engine could not resolve a cluster (see DESIGN.md limits)")
+    rep = _medoid_rep(engine.DeviceBatch.from_host(csr))
     print("".join(f"{cl}\n{n}\n" for cl, n in zip(ids, sizes.tolist())), end="")
     print(len(ids))
     write_chosen(outputfile, flat, records[rep])
@@ -168,9 +172,7 @@ def _main_device(inputfile, outputfile):
     if got is None:
         return False
     batch, meta = got
-    rep, _ = engine.medoid(batch, TOLERANCE).to_host()
-    if np.any(rep < 0):
-        raise RuntimeError("medoid engine could not resolve a cluster (see DESIGN.md limits)")
+    rep = _medoid_rep(batch)
     ids, sizes = meta["ids"], meta["sizes"]
     print("".join(f"{cl}\n{n}\n" for cl, n in zip(ids, sizes.tolist())), end="")
     print(len(ids))

@@ -28,10 +28,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib, engine
-from .csr import SpectraCSR
-
-_IN_FIELDS = (("cluster_off", np.int64), ("spec_off", np.int64), ("mz", np.float64), ("inten", np.float64),
-              ("prec_mz", np.float64), ("charge", np.int32), ("rt", np.float64))
+from .csr import CSR_FIELDS, SpectraCSR, csr_lengths
 
 
 def plan_chunks(cluster_off: np.ndarray, spec_off: np.ndarray, chunk_bytes: int):
@@ -61,16 +58,6 @@ class _Slot:
     chunk: tuple = None             # (c0, c1) it holds
 
 
-def _offsets(cap_c, cap_s, cap_p):
-    sizes = {"cluster_off": 8 * (cap_c + 1), "spec_off": 8 * (cap_s + 1), "mz": 8 * cap_p, "inten": 8 * cap_p,
-             "prec_mz": 8 * cap_s, "charge": 4 * cap_s, "rt": 8 * cap_s}
-    off, o = {}, 0
-    for name, _ in _IN_FIELDS:
-        off[name] = o
-        o += (sizes[name] + 255) & ~255
-    return off, o
-
-
 class HostPipeline:
     """bin-mean + medoid (the headline's step) over a host CSR, chunked and overlapped."""
 
@@ -94,13 +81,13 @@ class HostPipeline:
             return
         self.slots = []
         torch.cuda.empty_cache()
-        off, total = _offsets(cap_c, cap_s, cap_p)
-        sizes = {"cluster_off": cap_c + 1, "spec_off": cap_s + 1, "mz": cap_p, "inten": cap_p, "prec_mz": cap_s,
-                 "charge": cap_s, "rt": cap_s}
+        lengths = csr_lengths(cap_c, cap_s, cap_p)
+        nbytes = {name: lengths[name] * np.dtype(dt).itemsize for name, dt in CSR_FIELDS}
+        off, total = engine.aligned_layout(nbytes.items())
         for _ in range(2):
             raw = torch.empty(max(total, 256), dtype=torch.uint8, device=self.device)
-            views = {name: raw[off[name]:off[name] + sizes[name] * np.dtype(dt).itemsize].view(
-                getattr(torch, np.dtype(dt).name)) for name, dt in _IN_FIELDS}
+            views = {name: raw[off[name]:off[name] + nbytes[name]].view(engine.dtype_of(np.dtype(dt)))
+                     for name, dt in CSR_FIELDS}
             self.slots.append(_Slot(raw, views))
         self.cap = (cap_c, cap_s, cap_p)
 
@@ -136,26 +123,17 @@ class HostPipeline:
         s0, s1 = int(csr.cluster_off[c0]), int(csr.cluster_off[c1])
         p0 = int(csr.spec_off[s0])
         C, S, P = c1 - c0, s1 - s0, int(csr.spec_off[s1]) - p0
-        t = {name: slot.views[name][:n] for name, n in (("cluster_off", C + 1), ("spec_off", S + 1), ("mz", P),
-                                                          ("inten", P), ("prec_mz", S), ("charge", S), ("rt", S))}
+        t = {name: slot.views[name][:n] for name, n in csr_lengths(C, S, P).items()}
         t.update(n_clusters=C, n_spectra=S, n_peaks=P)
         return engine.DeviceBatch(t, csr.cluster_off[c0:c1 + 1] - s0, csr.spec_off[s0:s1 + 1] - p0, 0.0,
                                   buffers=slot.bufs)
 
     def _outputs(self, slot: _Slot, batch):
         """Capacity output tensors of the slot, sized for the largest chunk."""
-        import torch
-
         cap_c, _, cap_p = self.cap
         if slot.bm is None:
-            dev = self.device
-            slot.bm = engine.PeaksResult(None, torch.empty(max(cap_p, 1), dtype=torch.float64, device=dev),
-                                         torch.empty(max(cap_p, 1), dtype=torch.float64, device=dev),
-                                         torch.zeros(max(cap_c, 1), dtype=torch.int64, device=dev),
-                                         torch.zeros(max(cap_c, 1), dtype=torch.int32, device=dev),
-                                         torch.empty(max(cap_c, 1), dtype=torch.float64, device=dev),
-                                         torch.zeros(max(cap_c, 1), dtype=torch.int32, device=dev))
-            slot.md = engine.MedoidResult(torch.empty(max(cap_c, 1), dtype=torch.int64, device=dev), None)
+            slot.bm = engine.alloc_peaks(self.device, cap_p, cap_c)
+            slot.md = engine.alloc_medoid(self.device, cap_c)
         slot.bm.batch = batch
         return slot.bm, slot.md
 
@@ -219,10 +197,10 @@ class HostPipeline:
                     rep = slot.md.rep[:Cc].cpu().numpy()
                 res["rep"][c0:c1] = np.where(rep >= 0, rep + co[c0], rep)
                 kept[0] = k0 + n
-                # the medoid's run-time deferrals (REP_DEFERRED / REP_ARENA): the chunk is
-                # re-run by the checked call after the overlapped loop (redo), so the
-                # copy and compute streams never drain here
-                if np.any((rep == engine.REP_DEFERRED) | (rep == engine.REP_ARENA)):
+                # the medoid's run-time deferrals: the chunk is re-run by the checked call
+                # after the overlapped loop (redo), so the copy and compute streams never
+                # drain here
+                if engine.medoid_unresolved(rep):
                     redo.append(i)
             tm["readback_s"] += time.perf_counter() - t0
 
