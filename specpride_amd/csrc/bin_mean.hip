@@ -606,13 +606,32 @@ __device__ __forceinline__ int reg_prefix_md(BinRegSmem& L, int* md_total) {
 
 // What the fused pass's register path hands the medoid (bin_mean_reg_path_t<true>):
 // the medoid's tolerance in, and out: `out` (a peak's ceil(mz/tol) outside
-// [0, 32,768): the medoid reads the m/z itself), K (its occupied bins) and this lane's
-// spectrum [rlo, rhi) (lane j: spectrum min(j, n-1)), relative to the cluster's first peak.
+// [0, 32,768): the medoid reads the m/z itself) and K (its occupied bins).  (The spectrum
+// offsets the medoid needs it reads from the cluster's RegHeader again.)
 struct MdSide {
   double tol, inv_tol;
   int out, K;
-  int32_t rlo, rhi;
 };
+
+// A cluster's header as the fused pass's persistent loop prefetches it into LDS while
+// the cluster before it is processed (fused.hip, FusedPrefetch): everything the register
+// path's set-up reads from global memory, so the set-up of bin_mean_reg_path_t<true> waits
+// for no load.  n = BR_NMAX + 1 stands for "0 or more than BR_NMAX spectra" (kNotHere):
+// then only c and s0 are set.
+struct RegHeader {
+  int64_t s0, p0, p1;         // first spectrum; the cluster's peak range
+  int32_t c;                  // the cluster (-1: none left for this workgroup)
+  int32_t n;                  // spectra
+  int32_t rel[BR_NMAX + 2];   // spectrum j's first peak, relative to p0; rel[n] = p1 - p0
+  int32_t charge[BR_NMAX];
+  double prec[BR_NMAX];
+};
+
+__device__ __forceinline__ int64_t uniform64(int64_t x) {  // lane-uniform value -> SGPR pair
+  const uint64_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)x);
+  const uint64_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)x >> 32));
+  return (int64_t)(lo | (hi << 32));
+}
 
 // the register path's step loops: n <= BR_NMAX steps, uniform early exit
 template <class F>
@@ -630,35 +649,36 @@ __device__ __forceinline__ void reg_steps(int n, F&& f) {
 template <bool kMd>
 __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const BinMeanParams& P, BinRegSmem& L,
                                                        int64_t c, const PeaksOut& out, double* prec_out,
-                                                       int32_t* charge_out, int32_t (&code)[BR_NMAX], MdSide* md) {
+                                                       int32_t* charge_out, int32_t (&code)[BR_NMAX], MdSide* md,
+                                                       const RegHeader* hd = nullptr) {
   const int tid = threadIdx.x, lane = lane_id(), wid = wave_id();
   // spectra whose m/z phase A keeps for phase C (the fused pass needs registers for
   // its medoid bins in phase A)
   constexpr int KM = kMd ? SPX_BR_KM_MD : BR_KM;
   constexpr int PFA = kMd ? SPX_BR_PFA_MD : BR_PFA;  // phase-A ring depth
-  const int64_t s0 = v.cluster_off[c], s1 = v.cluster_off[c + 1], n64 = s1 - s0;
+  // kMd (the fused pass): the header is in LDS already, prefetched while the cluster
+  // before this one was processed (RegHeader), and the set-up waits for no global load
+  const int hn = kMd ? __builtin_amdgcn_readfirstlane(hd->n) : 0;
+  const int64_t s0 = kMd ? int64_t(0) : v.cluster_off[c], s1 = kMd ? (int64_t)hn : v.cluster_off[c + 1], n64 = s1 - s0;
   if (n64 < 1 || n64 > BR_NMAX || P.n_words > BM_WMAX) return kNotHere;
   const int n = (int)n64;
-  const int64_t p0 = v.spec_off[s0], p1 = v.spec_off[s1];
+  const int64_t p0 = kMd ? uniform64(hd->p0) : v.spec_off[s0], p1 = kMd ? uniform64(hd->p1) : v.spec_off[s1];
   if (p1 == p0 || p1 - p0 >= (int64_t(1) << 28)) return kNotHere;
   // lane j of every wave: spectrum j's [lo, hi) relative to p0, charge, precursor
   const int jl = lane < n ? lane : n - 1;
-  const int32_t rlo = (int32_t)(v.spec_off[s0 + jl] - p0), rhi = (int32_t)(v.spec_off[s0 + jl + 1] - p0);
-  const int32_t z0 = v.charge[s0];
+  const int32_t rlo = kMd ? hd->rel[jl] : (int32_t)(v.spec_off[s0 + jl] - p0),
+                rhi = kMd ? hd->rel[jl + 1] : (int32_t)(v.spec_off[s0 + jl + 1] - p0);
+  const int32_t z0 = kMd ? hd->charge[0] : v.charge[s0];
   const bool mine = lane < n;
-  const int32_t zl = v.charge[s0 + jl];
-  const double pl = v.prec_mz[s0 + jl];
+  const int32_t zl = kMd ? hd->charge[jl] : v.charge[s0 + jl];
+  const double pl = kMd ? hd->prec[jl] : v.prec_mz[s0 + jl];
   if (__ballot(mine & ((rhi - rlo) > BM_FASTLEN)) != 0ull) return kNotHere;  // uniform (same in every wave)
   if (__ballot(mine & (zl != z0)) != 0ull) {  // binning.py:205-206: nothing emitted
     if (tid == 0) { out.count[c] = 0; prec_out[c] = __longlong_as_double(0x7ff8000000000000ll); charge_out[c] = 0; }
     return kMixedCharge;
   }
   if (wid == 0 && mine) L.prec[lane] = pl;
-  if constexpr (kMd) {
-    md->rlo = rlo;
-    md->rhi = rhi;
-    reinterpret_cast<uint4*>(L.u.b.mdbits)[tid] = make_uint4(0u, 0u, 0u, 0u);
-  }
+  if constexpr (kMd) reinterpret_cast<uint4*>(L.u.b.mdbits)[tid] = make_uint4(0u, 0u, 0u, 0u);
   {
     uint4* z = reinterpret_cast<uint4*>(L.u.b.bits) + tid * (BR_WPT / 4);
 #pragma unroll
@@ -866,7 +886,7 @@ __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const B
                                    out.inten + p0);
   if (tid == 0) {
     out.count[c] = total;
-    charge_out[c] = z0;
+    charge_out[c] = kMd ? hd->charge[0] : z0;  // (kMd: from the header again, no register through A-D)
     prec_out[c] = pw_sum_small([&](int64_t j) { return L.prec[j]; }, n) / (double)n;  // np.mean (binning.py:224)
   }
   return kOk;

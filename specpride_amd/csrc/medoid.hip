@@ -234,9 +234,17 @@ struct MedoidRegSmem {
 // counts, the reference's distance matrix, the pairwise-tree totals and the
 // lowest-index argmin.  Shared by medoid_small_body and the fused pass's
 // medoid_from_codes (fused.hip), so both give the same bits.
-template <int BLOCK, int UMAX, int KWMAX>
+struct MedoidNoHook {
+  __device__ __forceinline__ void operator()(int) const {}
+};
+// hook(0) runs right after the barrier that opens P4 and hook(1) right after the one that
+// closes it (every wave calls them, no barrier inside): the fused pass's persistent loop
+// issues the steps of its next-cluster prefetch there, each a whole phase before the next
+// full barrier (which waits for the wave's outstanding loads).
+template <int BLOCK, int UMAX, int KWMAX, class Hook = MedoidNoHook>
 __device__ __forceinline__ void medoid_tail(MedoidRegSmem<BLOCK, UMAX, KWMAX>& L, int n, int KW, int64_t s0,
-                                            int64_t c, int64_t* rep, double* totals_out) {
+                                            int64_t c, int64_t* rep, double* totals_out,
+                                            const Hook& hook = Hook{}) {
   constexpr int PMAX = UMAX * BLOCK;
   const int tid = threadIdx.x, lane = lane_id(), wid = wave_id();
   // each spectrum's exact reciprocal for P4's quotients (totals is free until P5;
@@ -248,6 +256,7 @@ __device__ __forceinline__ void medoid_tail(MedoidRegSmem<BLOCK, UMAX, KWMAX>& L
   }
   __syncthreads();
   SPX_STAMP2(4, -1);
+  if constexpr (!std::is_same<Hook, MedoidNoHook>::value) hook(0);
 
   auto row_start = [&](int i) { return i * n - (i * (i - 1)) / 2; };
   // the matrix cores for the register kernel's P4; the wide kernel (up to 95 row words,
@@ -341,6 +350,7 @@ __device__ __forceinline__ void medoid_tail(MedoidRegSmem<BLOCK, UMAX, KWMAX>& L
   __syncthreads();
   // D(a, b) of the reference's dense matrix: the upper triangle incl. the
   // diagonal, zeros below (most_similar_representative.py:91-93)
+  if constexpr (!std::is_same<Hook, MedoidNoHook>::value) hook(1);
 
   SPX_STAMP2(5, 6);
   // P5: totals, one lane per spectrum (n <= 64): wave 0 sums row i, wave 1 column i, each

@@ -321,7 +321,7 @@ int kept_fold_enabled() {
 // slots of BinMeanWs::counters (zeroed by the call's opening memset)
 enum BmCounter {
   kBmcDeferred = 0,       // clusters past the wide kernel: the main chain's kept-bin fold list
-  kBmcUnused = 1,
+  kBmcUnused = 1,         // the fused head's cluster queue (bin_mean_medoid_kernel); unused otherwise
   kBmcSplitClusters = 2,  // planned split clusters
   kBmcSplitRanges = 3,
   kBmcGlobal = 4,         // the global kernel's list
@@ -439,8 +439,10 @@ BinMeanWs carve_bin_mean(Carver& w, const spx_csr* csr, const spx_bin_params* pa
 // The launch that replaces the register kernel's (spx_bin_mean_medoid: the fused
 // kernel), given the call's views; nullptr = bin_mean_reg_kernel itself.
 struct BinMeanHead {
+  // `queue`: a counter of the workspace that the opening memset zeroes (kBmcUnused)
   int (*launch)(void* ctx, const spx::CsrView& V, const spx::BinMeanParams& P, const spx::PeaksOut& O,
-                double* prec_out, int32_t* charge_out, int32_t* status, const spx::StripedList& rest, hipStream_t s);
+                double* prec_out, int32_t* charge_out, int32_t* status, const spx::StripedList& rest, int32_t* queue,
+                hipStream_t s);
   void* ctx;
 };
 
@@ -545,7 +547,8 @@ int bin_mean_impl(const spx_csr* csr, const spx_bin_params* params, const spx_ba
       if (int rc = side.wait_mid(s)) return rc;
     }
     if (head) {
-      if (int rc = head->launch(head->ctx, V, P, O, prec_out, charge_out, status, W.rest, s)) return rc;
+      if (int rc = head->launch(head->ctx, V, P, O, prec_out, charge_out, status, W.rest, cnt(kBmcUnused), s))
+        return rc;
     } else {
       if (int rc = SPX_LAUNCH_TIMED(ProfScope(kProfBinMeanReg, s), bin_mean_reg_kernel, dim3((unsigned)C), bbm, s, V, P,
                                     O, prec_out, charge_out, status, W.rest))
@@ -880,13 +883,53 @@ struct FusedCtx {
   const int32_t* bm_counts;  // set by the launch: the bin-mean hand-off list's stripe counters
 };
 
+// The fused kernel is persistent: its grid is the workgroups the device holds at once (CUs x
+// workgroups per CU from the occupancy query, asked once per device), at most C.  Its
+// workgroups never wait on one another, so any grid >= 1 gives the same results.
+// SPX_FU_GRID (environment, tests only) caps it, so one workgroup walks many clusters of a
+// small batch (1: the whole batch, in order).
+int64_t fused_grid(int64_t C) {
+  static std::mutex mu;
+  static int64_t slots[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0) return -1;
+  int64_t g = 0;
+  {
+    std::lock_guard<std::mutex> lock(mu);
+    int64_t& cached = slots[dev < 64 ? dev : 63];
+    if (dev >= 64 || cached == 0) {
+      int cus = 0, per_cu = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, spx::bin_mean_medoid_kernel, spx::BM_BLOCK, 0) !=
+              hipSuccess ||
+          cus < 1 || per_cu < 1)
+        return -1;
+      cached = (int64_t)cus * per_cu;
+    }
+    g = cached;
+  }
+  if (const char* e = std::getenv("SPX_FU_GRID")) {
+    const long long v = std::strtoll(e, nullptr, 10);
+    if (v > 0) g = std::min<int64_t>(g, v);
+  }
+  return std::max<int64_t>(1, std::min(g, C));
+}
+
 int fused_head(void* ctx, const spx::CsrView& V, const spx::BinMeanParams& P, const spx::PeaksOut& O, double* prec_out,
-               int32_t* charge_out, int32_t* status, const spx::StripedList& rest, hipStream_t s) {
+               int32_t* charge_out, int32_t* status, const spx::StripedList& rest, int32_t* queue, hipStream_t s) {
   FusedCtx& F = *static_cast<FusedCtx*>(ctx);
   F.bm_counts = rest.counts;
-  return SPX_LAUNCH_TIMED(ProfScope(kProfBinMeanMedoid, s), bin_mean_medoid_kernel, dim3((unsigned)F.C),
-                          dim3(spx::BM_BLOCK), s, V, P, O, prec_out, charge_out, status, rest, F.md->P, F.rep, F.totals,
-                          F.md->wide);
+  const int64_t grid = fused_grid(F.C);
+  if (grid < 1) {
+    if (int rc = check_launch("spx_bin_mean_medoid occupancy query")) return rc;
+    return fail(SPX_EHIP, "spx_bin_mean_medoid: occupancy query failed");
+  }
+  // the queue head is 32-bit and every workgroup claims once past the end
+  if (F.C > (int64_t)INT32_MAX - grid) return fail(SPX_EINVAL, "spx_bin_mean_medoid: too many clusters");
+  const spx::FusedArgs A{V,        P,     O,        prec_out,   charge_out, status, rest, F.md->P,
+                         F.rep,    F.totals, F.md->wide, reinterpret_cast<uint32_t*>(queue)};
+  return SPX_LAUNCH_TIMED(ProfScope(kProfBinMeanMedoid, s), bin_mean_medoid_kernel, dim3((unsigned)grid),
+                          dim3(spx::BM_BLOCK), s, A);
 }
 
 // ------------------------------------------------------------ binned cosine

@@ -45,7 +45,27 @@ __device__ unsigned long long* g_spx_stamps;
 #endif
 // A stamp that the fused pass's diagnostic build (-DSPX_STAMPS -DSPX_STAMPS_FU) records at
 // index `fu` instead of `other` (-1: none), so its eight slots span both methods' phases.
-#ifdef SPX_STAMPS_FU
+// The fused kernel is persistent (one workgroup walks many clusters), so its stamps go to
+// the row of the cluster `c` in scope at the stamp, not to the workgroup's.
+// -DSPX_STAMPS_FU_SETUP moves slot 1 from the end of phase A to the end of the set-up
+// (p0->p1 is then the set-up alone, p1->p2 phases A and B).
+#if defined(SPX_STAMPS) && defined(SPX_STAMPS_FU)
+#define SPX_STAMP_AT(row, k)                                                                    \
+  do {                                                                                          \
+    if (threadIdx.x == 0 && g_spx_stamps)                                                       \
+      g_spx_stamps[(size_t)(row) * 8 + (k)] = (unsigned long long)__builtin_amdgcn_s_memtime(); \
+  } while (0)
+#ifdef SPX_STAMPS_FU_SETUP
+#define SPX_STAMP_FU_SLOT(other, fu) ((other) == 1 && (fu) < 0 ? 1 : ((fu) == 1 ? -1 : (fu)))
+#else
+#define SPX_STAMP_FU_SLOT(other, fu) (fu)
+#endif
+#define SPX_STAMP2(other, fu)                                                          \
+  do {                                                                                 \
+    if (SPX_STAMP_FU_SLOT(other, fu) >= 0)                                             \
+      SPX_STAMP_AT(c, SPX_STAMP_FU_SLOT(other, fu) < 0 ? 0 : SPX_STAMP_FU_SLOT(other, fu)); \
+  } while (0)
+#elif defined(SPX_STAMPS_FU)
 #define SPX_STAMP2(other, fu) \
   do {                        \
     if ((fu) >= 0) SPX_STAMP((fu) < 0 ? 0 : (fu)); \
