@@ -678,6 +678,11 @@ __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const B
     return kMixedCharge;
   }
   if (wid == 0 && mine) L.prec[lane] = pl;
+  // one register for the offsets from here on: lane j <= n holds spectrum j's first peak
+  // (lane n, and every lane past it, the cluster's end), so spectrum j is
+  // [readlane(rel, j), readlane(rel, j + 1)) and a step loop carries the second read
+  // into its next step: one v_readlane per step, not two
+  const int32_t rel = mine ? rlo : rhi;
   if constexpr (kMd) reinterpret_cast<uint4*>(L.u.b.mdbits)[tid] = make_uint4(0u, 0u, 0u, 0u);
   {
     uint4* z = reinterpret_cast<uint4*>(L.u.b.bits) + tid * (BR_WPT / 4);
@@ -701,26 +706,28 @@ __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const B
   // register a merge of two values, which compiles to a wait right after issue).
   const __amdgpu_buffer_rsrc_t rmz = bf_rsrc(v.mz + p0, (int)(p1 - p0));
   const __amdgpu_buffer_rsrc_t rit = bf_rsrc(v.inten + p0, (int)(p1 - p0));
+  // (a ring's tail prefetch, j >= n, starts at the cluster's end: out of range, no traffic)
   auto boffb = [&](int j) -> int {  // byte offset of this lane's peak of spectrum j
-    const int jj = j < n ? j : n - 1;
-    return (__builtin_amdgcn_readlane(rlo, jj) + fpos) * 8;
+    return (__builtin_amdgcn_readlane(rel, j < n ? j : n) + fpos) * 8;
   };
 
   // ---- A: bins, last-in-bin, occupancy, codes (branch-free per lane)
   double mk[KM > 0 ? KM : 1];  // m/z of spectra 0..BR_KM-1, kept from phase A
   uint32_t* bm32 = L.u.b.bits;
-  int bad = 0, mdout = 0;
+  int bad = 0, rare = 0;
   {
     // ring slot: this lane's m/z of spectrum j and the spectrum's length (read
     // once, when the load is issued)
     double ra[PFA];
     int rl[PFA];
+    // called for j = 0, 1, 2, ... in order: `ea` is spectrum j's first peak on entry
+    // and spectrum j + 1's on return (j >= n: the cluster's end, an empty spectrum)
+    int ea = __builtin_amdgcn_readlane(rel, 0);
     auto fetch = [&](int j, double& m, int& len) __attribute__((always_inline)) {
-      const int jj = j < n ? j : n - 1;
-      const int a = __builtin_amdgcn_readlane(rlo, jj), e = __builtin_amdgcn_readlane(rhi, jj);
-      const int k = a + fpos;
-      len = e - a;
-      m = bf_load(rmz, k * 8, 0);
+      const int a = ea;
+      ea = __builtin_amdgcn_readlane(rel, j + 1 < n ? j + 1 : n);
+      len = ea - a;
+      m = bf_load(rmz, (a + fpos) * 8, 0);
     };
 #pragma unroll
     for (int j = 0; j < BR_NMAX; ++j) code[j] = -1;
@@ -728,17 +735,30 @@ __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const B
       constexpr int j = decltype(jc)::value;
       if constexpr (j < KM) mk[j] = m;
       const bool act = fpos < len;
-      const bool inr = act & (m >= P.minimum) & (m < P.maximum);
-      const int32_t kb = bin_small(m, P);  // used only where inr
+      const bool ge = m >= P.minimum;
+      const bool inr = act & ge & (m < P.maximum);
+      // used only where inr.  A NaN m/z fails the band test, so its check rides the
+      // division path and the hot path has no compare for it; `rare` is written on the
+      // two division paths only (bit 0: a NaN m/z, bit 1: a medoid bin out of range),
+      // so `bad` stays a lane mask in scalar registers.  The NaN bit needs no
+      // owner-and-active mask: every m/z a lane loads is a peak of this cluster (or
+      // the 0 read past its end), which the lane that owns it sees as well.
+      const int32_t kb = trunc_div_small_or(m - P.minimum, P.binsize, P.inv_binsize,
+                                            [&]() __attribute__((always_inline)) { rare |= (int)(m != m); });
       // inactive lanes (past the spectrum's end) carry INT_MAX: the last active
-      // peak's neighbour then always differs from it, and never sorts below it
-      const int32_t key = inr ? kb : ((act & (m < P.minimum)) ? -1 : 0x7fffffff);
+      // peak's neighbour then always differs from it, and never sorts below it.
+      // (A NaN carries -1 here, where it carried INT_MAX: its cluster is deferred
+      // whatever its key, by `bad` on the lane that owns it.)
+      // (below the range: active and not `ge`, on the two compares' lane masks in
+      // scalar registers -- written as a predicate it compiles to a third compare)
+      const bool below = __builtin_amdgcn_inverse_ballot_w64(__builtin_amdgcn_ballot_w64(act) &
+                                                             ~__builtin_amdgcn_ballot_w64(ge));
+      const int32_t key = inr ? kb : (below ? -1 : 0x7fffffff);
       const int32_t kn = wave_next(key, 0x7fffffff);
-      bad |= (int)(owner & act & ((m != m) | (key > kn)));
+      bad |= (int)(owner & act & (key > kn));
       const bool valid = owner & inr & (kn != key);  // the last peak of its bin (binning.py:197-199)
-      // a lane without a contribution ORs 0 into a word of its own (same-address
-      // LDS atomics serialise; distinct words do not)
-      atomicOr(&bm32[valid ? key >> 5 : lane], valid ? 1u << (key & 31) : 0u);
+      // a lane without a contribution issues nothing (exec-masked)
+      if (valid) atomicOr(&bm32[key >> 5], 1u << (key & 31));
       if constexpr (kMd) {
         // the medoid's bin of the same peak, ceil(mz / tol) exactly (md_bin): the
         // reciprocal product where it is certain, else the division (~1 peak in 10^7)
@@ -750,13 +770,20 @@ __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const B
         if (__builtin_expect(mact & !((f > kDivBand) & (f < 1.0 - kDivBand) & (mb < 32u * BR_MDW32)), 0)) {
           const int64_t bb = ceil_div_exact(m, md->tol, md->inv_tol);
           const bool in = bb >= 0 && bb < 32 * BR_MDW32;
-          mdout |= !in;
+          rare |= in ? 0 : 2;
           mb = in ? (uint32_t)bb : 0u;
         }
-        // no peak here: 0 ORed into a word of the lane's own (same-address atomics serialise)
-        atomicOr(&L.u.b.mdbits[mact ? mb >> 5 : lane], mact ? 1u << (mb & 31) : 0u);
-        // bin-mean bin in the low 17 bits (0x1FFFF: no contribution), medoid bin above
-        code[j] = (valid ? key : 0x1FFFF) | (int32_t)((mact ? mb : 0u) << 17);
+        // (the select stands in front of the branch as a value of its own: merged into
+        // it, it compiles to two moves)
+        uint32_t mbs = mact ? mb : 0u;
+        asm volatile("" : "+v"(mbs));
+        if (mact) atomicOr(&L.u.b.mdbits[mbs >> 5], 1u << (mbs & 31));
+        // bin-mean bin in the low 17 bits (0x1FFFF: no contribution), medoid bin above:
+        // {mb, key << 15} >> 15 in one v_alignbit, no mask constant
+        // (the select opaque: folded into the shift it needs a constant in a register)
+        uint32_t ks = (uint32_t)(valid ? key : -1);
+        asm volatile("" : "+v"(ks));
+        code[j] = (int32_t)__builtin_amdgcn_alignbit(mbs, ks << 15, 15);
       } else {
         code[j] = valid ? key : -1;
       }
@@ -785,7 +812,7 @@ __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const B
   }
   if constexpr (kMd) {
     // one barrier for both votes: bit 0 bin-mean's (unsorted / NaN), bit 1 the medoid's
-    const int w = (__ballot(bad) != 0ull ? 1 : 0) | (__ballot(mdout) != 0ull ? 2 : 0);
+    const int w = (__ballot(bad | (rare & 1)) != 0ull ? 1 : 0) | (__ballot(rare & 2) != 0ull ? 2 : 0);
     if (lane == 0) L.votes[wid] = w;
     lds_barrier();
     int r = 0;
@@ -794,7 +821,7 @@ __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const B
     md->out = r >> 1;
     if (r & 1) return kDeferred;  // generic kernel redoes it
   } else {
-    if (block_any<BM_BLOCK, true>(bad, L.votes, 0)) return kDeferred;  // generic kernel redoes it
+    if (block_any<BM_BLOCK, true>(bad | rare, L.votes, 0)) return kDeferred;  // generic kernel redoes it
   }
   SPX_STAMP2(2, 1);
 
@@ -822,12 +849,18 @@ __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const B
           if (j0 + q < BR_NMAX) {
             const uint32_t lo = kMd ? (uint32_t)code[j0 + q] & 0x1FFFFu : (uint32_t)code[j0 + q];
             const uint32_t w = min(lo >> 5, (uint32_t)(BR_W32 + lane));
+            // the prefix's byte offset as a value of its own: one shift (derived from
+            // the word's address it compiled to 4w - 2w: a shift and a subtract)
+            uint32_t ph = w * 2u;
+            asm volatile("" : "+v"(ph));
             wb[q] = L.u.b.bits[w];
-            wp[q] = L.u.b.pre[w];
+            wp[q] = *reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(L.u.b.pre) + ph);
             if constexpr (kMd) {
               const uint32_t mw = (uint32_t)code[j0 + q] >> 22;  // the medoid bin's word
+              uint32_t mph = mw * 2u;
+              asm volatile("" : "+v"(mph));
               mwb[q] = L.u.b.mdbits[mw];
-              mwp[q] = L.u.b.mdpre[mw];
+              mwp[q] = *reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(L.u.b.mdpre) + mph);
             }
           }
         }
@@ -835,11 +868,12 @@ __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const B
         for (int q = 0; q < G; ++q) {
           if (j0 + q < BR_NMAX) {
             const uint32_t b = (uint32_t)code[j0 + q];
-            const int32_t slot = (int32_t)wp[q] + __popc(wb[q] & ((1u << (b & 31)) - 1u));
+            // the bits below bit (b & 31): v_bfe_u32 takes its width modulo 32 itself
+            const int32_t slot = (int32_t)wp[q] + __popc(__builtin_amdgcn_ubfe(wb[q], 0u, b));
             if constexpr (kMd) {
               // the medoid column: rank of the bin among the cluster's medoid bins
               const uint32_t mb = b >> 17;
-              const uint32_t col = mwp[q] + __popc(mwb[q] & ((1u << (mb & 31)) - 1u));
+              const uint32_t col = mwp[q] + __popc(__builtin_amdgcn_ubfe(mwb[q], 0u, mb));
               code[j0 + q] = slot | (int32_t)(col << 16);
             } else {
               code[j0 + q] = slot;
@@ -868,7 +902,8 @@ __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const B
     if constexpr (kMd && (j & 1)) {
       // both slots used: spectra j-1 and j's medoid columns share code[j-1] (low, high
       // half) from here on, so code[j] is dead through phase D (registers for the emit)
-      code[j - 1] = (int32_t)(((uint32_t)code[j - 1] >> 16) | ((uint32_t)code[j] & 0xFFFF0000u));
+      // (one v_perm: bytes 3, 2 of code[j] over bytes 3, 2 of code[j - 1])
+      code[j - 1] = (int32_t)__builtin_amdgcn_perm((uint32_t)code[j], (uint32_t)code[j - 1], 0x07060302u);
     }
     BinAcc a = L.u.acc[slot];
     a.i = (float)((double)a.i + it);

@@ -159,11 +159,11 @@ __device__ __forceinline__ bool medoid_from_codes(int64_t* rep, double* totals_o
     if (tid == 0) defer(c, s0, n);
     return false;
   }
-  // lane j: spectrum min(j, n - 1)'s peaks [rlo, rhi), relative to the cluster's first
-  const int jl = lane < n ? lane : n - 1;
-  const int32_t rlo = hd.rel[jl], rhi = hd.rel[jl + 1];
+  // lane j <= n: spectrum j's first peak relative to the cluster's first (lane n, and
+  // every lane past it: the cluster's end)
+  const int32_t rel = hd.rel[lane < n ? lane : n];
   // spectrum offsets (lane j < n: spectrum j's start; lane n: spectrum n-1's end)
-  if (tid <= n) L.soff[tid] = tid < n ? rlo : rhi;
+  if (tid <= n) L.soff[tid] = rel;
   for (int w = tid; w < n * KW; w += MD_BLOCK) L.u.a.rows[w] = 0ull;
   __syncthreads();
   // each prefetch step goes out right AFTER a full barrier (which waits for the wave's
@@ -173,9 +173,17 @@ __device__ __forceinline__ bool medoid_from_codes(int64_t* rep, double* totals_o
   const uint32_t swz_m = swz_nw >= 32u ? 31u : (1u << (31 - __clz((int)swz_nw))) - 1u;  // 2^k - 1 < swz_nw
   const int fpos = wid * (kWave - 1) + lane;
   const bool owner = lane < kWave - 1;
+  int ea = __builtin_amdgcn_readlane(rel, 0);  // spectrum j's first peak, carried from step to step
+  const int kw8 = __builtin_amdgcn_readfirstlane(8 * KW);  // bytes per row, uniform
   reg_steps(n, [&](auto jc) __attribute__((always_inline)) {
     constexpr int j = decltype(jc)::value;
-    const int len = __builtin_amdgcn_readlane(rhi, j) - __builtin_amdgcn_readlane(rlo, j);
+    const int a = ea;
+    ea = __builtin_amdgcn_readlane(rel, j + 1);
+    const int len = ea - a;
+    // the row's byte offset is uniform: pinned to a scalar register it joins the address in
+    // one shift-add (left to the compiler it became a constant move and a 24-bit mad)
+    int row = j * kw8;
+    asm volatile("" : "+s"(row));
     if (owner & (fpos < len)) {
       // phase C packed the columns of spectra 2k, 2k+1 into code[2k] (low, high half);
       // a last even spectrum (n odd) keeps its (slot, column) code
@@ -185,7 +193,7 @@ __device__ __forceinline__ bool medoid_from_codes(int64_t* rep, double* totals_o
       // the register kernel's P3 word swizzle (a bijection per bit position)
       uint32_t wq = (col >> 5) + (col & swz_m);
       wq = min(wq, wq - swz_nw);
-      atomicOr(reinterpret_cast<uint32_t*>(&L.u.a.rows[__mul24(j, KW)]) + wq, 1u << (col & 31));
+      atomicOr(reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(L.u.a.rows) + row) + wq, 1u << (col & 31));
     }
   });
   SPX_STAMP2(-1, 5);

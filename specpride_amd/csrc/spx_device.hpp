@@ -426,6 +426,21 @@ __device__ __forceinline__ int32_t trunc_div_small(double x, double w, double in
   return (int32_t)trunc(x / w);
 }
 
+// trunc_div_small that runs on_div() on the lanes that take the division.  A NaN x
+// makes f NaN, which fails the band test: a caller's NaN check can sit in on_div()
+// and cost the fast path nothing.
+template <class OnDiv>
+__device__ __forceinline__ int32_t trunc_div_small_or(double x, double w, double inv_w, const OnDiv& on_div) {
+  const double q = x * inv_w;
+  double t = trunc(q);
+  const double f = q - t;
+  if (__builtin_expect(!(f > 0x1p-30 && f < 1.0 - 0x1p-30), 0)) {
+    t = trunc(x / w);
+    on_div();
+  }
+  return (int32_t)t;
+}
+
 __device__ __forceinline__ int64_t floor_div_exact(double x, double w, double inv_w) {
   const double q = x * inv_w;
   const double t = floor(q);
