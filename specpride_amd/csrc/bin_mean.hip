@@ -683,6 +683,38 @@ __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const B
   // [readlane(rel, j), readlane(rel, j + 1)) and a step loop carries the second read
   // into its next step: one v_readlane per step, not two
   const int32_t rel = mine ? rlo : rhi;
+
+  const int fpos = wid * (kWave - 1) + lane;  // this lane's peak in every spectrum
+  const bool owner = lane < kWave - 1;
+  // Buffer descriptors over the cluster's peaks.  A lane past its spectrum's end
+  // reads the next spectrum's peak, or 0 past the cluster's end (out of the
+  // descriptor's range: no fault), so the offsets need no select; spectra past
+  // the cluster's last (j >= n, a ring's tail prefetch) re-read the last one.
+  // The ring's loads are unconditional (a conditional load makes its ring
+  // register a merge of two values, which compiles to a wait right after issue).
+  const __amdgpu_buffer_rsrc_t rmz = bf_rsrc(v.mz + p0, (int)(p1 - p0));
+  const __amdgpu_buffer_rsrc_t rit = bf_rsrc(v.inten + p0, (int)(p1 - p0));
+  // Phase A's ring slot: this lane's m/z of spectrum j and the spectrum's length (read
+  // once, when the load is issued).  The first PFA loads go out HERE, ahead of the
+  // set-up's LDS work: all they need is the header, and the header's checks (the
+  // cluster's size, the peak range the descriptor is sized by, a long spectrum, mixed
+  // charges) have all returned above.  The barrier below orders LDS only, so the loads
+  // travel while the bitmaps are zeroed (fused pass, 100k clusters: set-up + phase A
+  // 33.4k -> 31.1k cycles with the band edges below; profiles/fused_scalar_ab.txt).
+  double ra[PFA];
+  int rl[PFA];
+  // called for j = 0, 1, 2, ... in order: `ea` is spectrum j's first peak on entry
+  // and spectrum j + 1's on return (j >= n: the cluster's end, an empty spectrum)
+  int ea = __builtin_amdgcn_readlane(rel, 0);
+  auto fetch = [&](int j, double& m, int& len) __attribute__((always_inline)) {
+    const int a = ea;
+    ea = __builtin_amdgcn_readlane(rel, j + 1 < n ? j + 1 : n);
+    len = ea - a;
+    m = bf_load(rmz, (a + fpos) * 8, 0);
+  };
+#pragma unroll
+  for (int j = 0; j < PFA; ++j) fetch(j, ra[j], rl[j]);
+
   if constexpr (kMd) reinterpret_cast<uint4*>(L.u.b.mdbits)[tid] = make_uint4(0u, 0u, 0u, 0u);
   {
     uint4* z = reinterpret_cast<uint4*>(L.u.b.bits) + tid * (BR_WPT / 4);
@@ -696,16 +728,6 @@ __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const B
   lds_barrier();
   SPX_STAMP2(1, -1);
 
-  const int fpos = wid * (kWave - 1) + lane;  // this lane's peak in every spectrum
-  const bool owner = lane < kWave - 1;
-  // Buffer descriptors over the cluster's peaks.  A lane past its spectrum's end
-  // reads the next spectrum's peak, or 0 past the cluster's end (out of the
-  // descriptor's range: no fault), so the offsets need no select; spectra past
-  // the cluster's last (j >= n, a ring's tail prefetch) re-read the last one.
-  // The ring's loads are unconditional (a conditional load makes its ring
-  // register a merge of two values, which compiles to a wait right after issue).
-  const __amdgpu_buffer_rsrc_t rmz = bf_rsrc(v.mz + p0, (int)(p1 - p0));
-  const __amdgpu_buffer_rsrc_t rit = bf_rsrc(v.inten + p0, (int)(p1 - p0));
   // (a ring's tail prefetch, j >= n, starts at the cluster's end: out of range, no traffic)
   auto boffb = [&](int j) -> int {  // byte offset of this lane's peak of spectrum j
     return (__builtin_amdgcn_readlane(rel, j < n ? j : n) + fpos) * 8;
@@ -716,21 +738,18 @@ __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const B
   uint32_t* bm32 = L.u.b.bits;
   int bad = 0, rare = 0;
   {
-    // ring slot: this lane's m/z of spectrum j and the spectrum's length (read
-    // once, when the load is issued)
-    double ra[PFA];
-    int rl[PFA];
-    // called for j = 0, 1, 2, ... in order: `ea` is spectrum j's first peak on entry
-    // and spectrum j + 1's on return (j >= n: the cluster's end, an empty spectrum)
-    int ea = __builtin_amdgcn_readlane(rel, 0);
-    auto fetch = [&](int j, double& m, int& len) __attribute__((always_inline)) {
-      const int a = ea;
-      ea = __builtin_amdgcn_readlane(rel, j + 1 < n ? j + 1 : n);
-      len = ea - a;
-      m = bf_load(rmz, (a + fpos) * 8, 0);
-    };
 #pragma unroll
     for (int j = 0; j < BR_NMAX; ++j) code[j] = -1;
+    // The two reciprocal-product bands' edges (trunc_div_small's 2^-30, kDivBand) and the
+    // medoid's bin limit, held in scalar registers for the cluster: as literals the compiler
+    // builds each 64-bit edge with two scalar moves in EVERY step (9 scalar instructions of
+    // a step's 33).  What a step reads of P and md (minimum, maximum, inv_binsize, inv_tol)
+    // the compiler already keeps in scalar registers across the steps; binsize and tol are
+    // read on the out-of-line division paths only.
+    double bm_lo = 0x1p-30, bm_hi = 1.0 - 0x1p-30, md_lo = kDivBand, md_hi = 1.0 - kDivBand;
+    uint32_t md_lim = 32u * BR_MDW32;
+    asm volatile("" : "+s"(bm_lo), "+s"(bm_hi));
+    if constexpr (kMd) asm volatile("" : "+s"(md_lo), "+s"(md_hi), "+s"(md_lim));
     auto body = [&](auto jc, const double m, const int len) __attribute__((always_inline)) {
       constexpr int j = decltype(jc)::value;
       if constexpr (j < KM) mk[j] = m;
@@ -743,8 +762,19 @@ __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const B
       // so `bad` stays a lane mask in scalar registers.  The NaN bit needs no
       // owner-and-active mask: every m/z a lane loads is a peak of this cluster (or
       // the 0 read past its end), which the lane that owns it sees as well.
-      const int32_t kb = trunc_div_small_or(m - P.minimum, P.binsize, P.inv_binsize,
-                                            [&]() __attribute__((always_inline)) { rare |= (int)(m != m); });
+      // (trunc_div_small_or, spx_device.hpp, with the band's edges from the registers above)
+      int32_t kb;
+      {
+        const double x = m - P.minimum;
+        const double q = x * P.inv_binsize;
+        double t = trunc(q);
+        const double f = q - t;
+        if (__builtin_expect(!(f > bm_lo && f < bm_hi), 0)) {
+          t = trunc(x / P.binsize);
+          rare |= (int)(m != m);
+        }
+        kb = (int32_t)t;
+      }
       // inactive lanes (past the spectrum's end) carry INT_MAX: the last active
       // peak's neighbour then always differs from it, and never sorts below it.
       // (A NaN carries -1 here, where it carried INT_MAX: its cluster is deferred
@@ -767,7 +797,7 @@ __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const B
         const double t = ceil(q);
         const double f = t - q;
         uint32_t mb = (uint32_t)__double2int_rz(t);
-        if (__builtin_expect(mact & !((f > kDivBand) & (f < 1.0 - kDivBand) & (mb < 32u * BR_MDW32)), 0)) {
+        if (__builtin_expect(mact & !((f > md_lo) & (f < md_hi) & (mb < md_lim)), 0)) {
           const int64_t bb = ceil_div_exact(m, md->tol, md->inv_tol);
           const bool in = bb >= 0 && bb < 32 * BR_MDW32;
           rare |= in ? 0 : 2;
@@ -791,8 +821,6 @@ __device__ __forceinline__ int32_t bin_mean_reg_path_t(const CsrView& v, const B
       // live instead (50 SGPR pairs: spills)
       asm volatile("" : "+v"(code[j]));
     };
-#pragma unroll
-    for (int j = 0; j < PFA; ++j) fetch(j, ra[j], rl[j]);
     reg_steps(n, [&](auto jc) __attribute__((always_inline)) {
       constexpr int j = decltype(jc)::value;
       const double m = ra[j % PFA];
