@@ -24,8 +24,9 @@
 // the grid size is a tuning value only).  While a cluster's medoid runs -- the part of
 // a lifetime that issues no global load of its own -- the workgroup's last wave claims
 // the next cluster and fetches its header (offsets, charges, precursors: RegHeader,
-// bin_mean.hip) into the other of two LDS buffers, one dependent load per medoid phase,
-// so the next set-up reads LDS and waits for no round trip (FusedPrefetch).
+// bin_mean.hip) into the other of two LDS buffers -- the claim during the medoid's rows,
+// the dependent loads beside the two waves that compute the medoid's tail -- so the next
+// set-up reads LDS and waits for no round trip (FusedPrefetch).
 #include "bin_mean.hip"
 #include "medoid.hip"
 
@@ -44,9 +45,10 @@ union FusedSmem {
 };
 static_assert(BM_BLOCK == MD_BLOCK, "one workgroup shape for both bodies");
 
-// The next cluster's header, fetched by ONE wave (all 64 lanes active) in four steps that
-// the caller places at wave-uniform program points far enough apart for each step's loads
-// to have landed when the next one uses them:
+// The next cluster's header, fetched by ONE wave (all 64 lanes active) in four steps at
+// wave-uniform program points: the claim goes out a phase ahead (the medoid's rows), the
+// other three run back to back in the medoid's tail, where this wave has no other work and
+// waits for each step's loads itself:
 //   claim    the queue head's atomicAdd                       -> tc
 //   offsets  tc -> H->c; cluster_off[c], cluster_off[c + 1]   -> toff
 //   spectra  toff -> H->s0, H->n; spec_off, charge, prec_mz   -> tso, tz, tp
@@ -166,8 +168,8 @@ __device__ __forceinline__ bool medoid_from_codes(int64_t* rep, double* totals_o
   if (tid <= n) L.soff[tid] = rel;
   for (int w = tid; w < n * KW; w += MD_BLOCK) L.u.a.rows[w] = 0ull;
   __syncthreads();
-  // each prefetch step goes out right AFTER a full barrier (which waits for the wave's
-  // outstanding loads) and has a whole phase to land before the next one: P3, P4, P5-P6
+  // the claim goes out right AFTER a full barrier (which waits for the wave's outstanding
+  // loads) and has P3 to land; the other steps follow the barrier that opens the tail
   if (fused_prefetch_wave()) pf.claim(head, k);
   const uint32_t swz_nw = 2u * (uint32_t)KW;  // 32-bit words per row
   const uint32_t swz_m = swz_nw >= 32u ? 31u : (1u << (31 - __clz((int)swz_nw))) - 1u;  // 2^k - 1 < swz_nw
@@ -197,13 +199,15 @@ __device__ __forceinline__ bool medoid_from_codes(int64_t* rep, double* totals_o
     }
   });
   SPX_STAMP2(-1, 5);
-  medoid_tail<MD_BLOCK, MR_UMAX, MD_KWMAX>(L, n, KW, s0, c, rep, totals_out,
-                                           [&](int at) __attribute__((always_inline)) {
-                                             if (!fused_prefetch_wave()) return;
-                                             if (at == 0) pf.offsets(v, Hn);
-                                             else pf.spectra(v, Hn);
-                                           });
-  if (fused_prefetch_wave()) pf.commit(Hn);
+  // the tail's work is waves 0 and 1's (n <= 50 here): the prefetching wave runs the
+  // remaining steps on its own beside them, waiting for each step's loads (Hn lies outside
+  // the medoid's LDS, and the loop-top barrier publishes it)
+  medoid_tail<MD_BLOCK, MR_UMAX, MD_KWMAX>(L, n, KW, s0, c, rep, totals_out, [&]() __attribute__((always_inline)) {
+    if (!fused_prefetch_wave()) return;
+    pf.offsets(v, Hn);
+    pf.spectra(v, Hn);
+    pf.commit(Hn);
+  });
   return true;
 }
 

@@ -38,7 +38,7 @@ constexpr int MD_NMAX = 64;
 #define SPX_MD_MINW 7
 #endif
 #ifndef SPX_MD_MFMA_NMIN
-#define SPX_MD_MFMA_NMIN 32  // ... for clusters of more spectra than this
+#define SPX_MD_MFMA_NMIN 1  // the register tail for clusters of more spectra than this (1: all)
 #endif
 constexpr int MD_KWMAX = SPX_MD_KWMAX;  // row words (odd stride): <= 64 * MD_KWMAX occupied bins per small cluster
 
@@ -57,13 +57,17 @@ __device__ __forceinline__ double md_dist(uint32_t c, int64_t pi, int64_t pj) {
 // and one exact fma remainder step: equal to the IEEE quotient fl(c/q) for every
 // 0 <= c <= q <= 65,536 (all 2.1e9 pairs checked on the host), so the distances --
 // and with them the totals and representatives -- are md_dist's bit for bit.
-__device__ __forceinline__ double md_dist_r(uint32_t c, int pi, double ri, int pj, double rj) {
+// (cd: the count as a double -- the MFMA's f32 sums convert exactly)
+__device__ __forceinline__ double md_dist_rd(double cd, int pi, double ri, int pj, double rj) {
   const int q = pi < pj ? pi : pj;
-  const double cd = (double)c, qd = (double)q;
+  const double qd = (double)q;
   const double r = pi < pj ? ri : rj;
   const double y = cd * r;
   const double x = __builtin_fma(__builtin_fma(-y, qd, cd), r, y);
   return (pi == 0 || pj == 0) ? 1.0 : 1.0 - x;
+}
+__device__ __forceinline__ double md_dist_r(uint32_t c, int pi, double ri, int pj, double rj) {
+  return md_dist_rd((double)c, pi, ri, pj, rj);
 }
 // Both pairwise sums of thread i (row i: j >= i; column i: j <= i) in one pass
 // over j, for n <= 128 (numpy's leaf regime).  f(j) returns d(i, j) = d(j, i).
@@ -177,15 +181,16 @@ __device__ __forceinline__ void md_defer(int64_t c, int64_t s0, int n, int32_t* 
 //       set by 32-bit LDS atomics into words swizzled per bit position
 //       (a spectrum's neighbouring columns -- consecutive lanes --
 //       no longer serialise on one word)
-//   P4  pair counts: past 32 spectra on the matrix cores (FP4 0/1 Gram tiles, one
-//       per wave), else one thread per pair i <= j by AND + popcount;
-//       then d_ij = 1 - c_ij/min(p_i, p_j) (exact reciprocal form, md_dist_r) into
-//       the reference's n x n matrix (upper triangle incl. the diagonal, zeros
-//       below: most_similar_representative.py:91-93), aliasing the dead bitmap and rows
-//   P5  totals with numpy's pairwise tree (:98-100): one lane per spectrum, wave 0
-//       the rows, wave 1 the columns (8 strided accumulators combined
-//       ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), sequential tail), total = (row + col)/n
-//   P6  lowest index of the minimum (:103-110), wave 0 straight from P5's registers
+//   P4  pair counts on the matrix cores (FP4 0/1 Gram tiles, one wave per 32 columns);
+//       d_ij = 1 - c_ij/min(p_i, p_j) (exact reciprocal form, md_dist_r) of the
+//       reference's n x n matrix (upper triangle incl. the diagonal, zeros below:
+//       most_similar_representative.py:91-93) formed in the accumulator's lanes and
+//   P5  added at once into numpy's pairwise tree (:98-100): 8 strided accumulators
+//       split over a lane pair, combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), sequential
+//       tail, total = (row + col)/n -- no distance matrix in LDS (medoid_tail_regs)
+//   P6  lowest index of the minimum (:103-110), from the same registers
+//       (the wide kernel: one thread per pair i <= j by AND + popcount, the matrix in
+//       LDS over the dead rows, one lane per spectrum for the sums)
 // Deferred (to the wide kernel, then the large path): n > 64, > MR_UMAX*256 peaks, a bin outside
 // [0, 65,536), > 64 * MD_KWMAX distinct bins.
 constexpr int MR_UMAX = 48;                  // peaks per thread (12,288 per cluster)
@@ -235,12 +240,151 @@ struct MedoidRegSmem {
 // lowest-index argmin.  Shared by medoid_small_body and the fused pass's
 // medoid_from_codes (fused.hip), so both give the same bits.
 struct MedoidNoHook {
-  __device__ __forceinline__ void operator()(int) const {}
+  __device__ __forceinline__ void operator()() const {}
 };
-// hook(0) runs right after the barrier that opens P4 and hook(1) right after the one that
-// closes it (every wave calls them, no barrier inside): the fused pass's persistent loop
-// issues the steps of its next-cluster prefetch there, each a whole phase before the next
-// full barrier (which waits for the wave's outstanding loads).
+
+// P4..P6 in registers, one wave per 32 columns (wave 0: spectra 0..31, wave 1: 32..63),
+// for the 256-thread kernels.  The wave computes the full 32 x 32 Gram tile of its columns
+// against each 32-row tile -- one v_mfma_scale_f32_32x32x64_f8f6f4 per 64-bin row word, FP4
+// 0/1 operands at unit scale, so the f32 sums are the integer counts |B_r ∩ B_j| -- and
+// folds the tile into the totals straight from the accumulator.  The C/D layout gives lane
+// (j = lane & 31, fh = lane >> 5) column j at rows (q & 3) + 8 * (q >> 2) + 4 * fh: of every
+// eight consecutive rows the fh = 0 lane holds the first four and the fh = 1 lane the
+// others, which are numpy's strided leaf accumulators r[0..3] and r[4..7] (index mod 8), met
+// in ascending order.  d is symmetric, so column j of the tile holds the terms of row sum j
+// (rows >= j) and of column sum j (rows <= j) of the reference's upper-triangular matrix:
+// both are summed at once, the other side's terms replaced by +0.0 (every partial sum is
+// >= +0.0, so adding it changes nothing).  Nothing is written to LDS before the result:
+// the rows stay in place, the distances never exist all at once.
+template <int BLOCK, int UMAX, int KWMAX>
+__device__ __forceinline__ void medoid_tail_regs(MedoidRegSmem<BLOCK, UMAX, KWMAX>& L, int n, int KW, int64_t s0,
+                                                 int64_t c, int64_t* rep, double* totals_out) {
+  const int lane = lane_id(), wid = wave_id();
+  const int fr = lane & 31, fh = lane >> 5;
+  const bool two = n > 32;  // uniform: two column waves, two row tiles each
+  double best = __longlong_as_double(0x7ff0000000000000ll);
+  int idx = 0x7fffffff;
+  if (wid == 0 || (two && wid == 1)) {  // wave-uniform
+    const int j = wid * 32 + fr;        // this lane's column (both halves of the wave)
+    const bool jv = j < n;
+    const int pj = L.soff[j + 1] - L.soff[j];  // (j <= 63: inside soff and totals for every lane)
+    const double rj = L.totals[j];
+    const unsigned long long* pb = L.u.a.rows + (jv ? j : 0) * KW;
+    const unsigned long long mb = jv ? ~0ull : 0ull;
+    // numpy's leaf sum: 8 strided accumulators over the indices below lim, then a sequential tail
+    const int lim = n >= 8 ? n - n % 8 : 0;
+    double ra[4], ca[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ra[i] = ca[i] = 0.0;
+    md_f32x16 acc;
+    const int ntile = two ? 2 : 1;
+    for (int t = 0; t < ntile; ++t) {  // uniform: row tile 0, then 1 -- each r[k] chain in index order
+      const int ia = t * 32 + fr;
+      const unsigned long long* pa = L.u.a.rows + (ia < n ? ia : 0) * KW;
+      const unsigned long long ma = ia < n ? ~0ull : 0ull;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
+      unsigned long long wa = pa[0] & ma, wb = pb[0] & mb;  // one word ahead
+      for (int w = 0; w < KW; ++w) {
+        const int wn = w + 1 < KW ? w + 1 : w;
+        const unsigned long long na = pa[wn] & ma, nb = pb[wn] & mb;
+        acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(md_frag4(wa, fh), md_frag4(wb, fh), acc, 4, 4, 0, 0,
+                                                              0, 0);
+        wa = na;
+        wb = nb;
+      }
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int r0 = t * 32 + 8 * g;
+        // uniform: lim is a multiple of 8, so a group of eight rows lies wholly below it or
+        // adds nothing to the strided accumulators (the group AT lim is the tail's, below)
+        if (r0 < lim) {
+          const int rb = r0 + 4 * fh;
+          int so[5];
+#pragma unroll
+          for (int i = 0; i < 5; ++i) so[i] = L.soff[rb + i];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int r = rb + i;
+            const double d = md_dist_rd((double)acc[4 * g + i], so[i + 1] - so[i], L.totals[r], pj, rj);
+            ra[i] += r >= j ? d : 0.0;
+            ca[i] += r <= j ? d : 0.0;
+          }
+        }
+      }
+    }
+    SPX_STAMP2(5, 6);
+    // fh = 0 holds (r0+r1)+(r2+r3), fh = 1 (r4+r5)+(r6+r7): one exchange, one add (the same
+    // bits in both halves: the addition commutes)
+    double rs = (ra[0] + ra[1]) + (ra[2] + ra[3]);
+    double cs = (ca[0] + ca[1]) + (ca[2] + ca[3]);
+    rs = rs + __shfl_xor(rs, 32, kWave);
+    cs = cs + __shfl_xor(cs, 32, kWave);
+    if (lim < n) {  // uniform
+      // the sequential tail, rows lim..n-1: they are the group at lim of the LAST tile (still
+      // in acc); indices lim..lim+3 sit in the fh = 0 lane and lim+4.. in fh = 1, so the sum
+      // runs on in fh = 0, is handed over once and finishes in fh = 1.  n < 8 is all tail.
+      const int gt = (lim & 31) >> 3;
+      float v[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = acc[i];
+#pragma unroll
+      for (int g = 1; g < 4; ++g) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = g == gt ? acc[4 * g + i] : v[i];
+      }
+      const int rb = lim + 4 * fh;  // rb + 4 <= 64: lim <= 56 here
+      int so[5];
+#pragma unroll
+      for (int i = 0; i < 5; ++i) so[i] = L.soff[rb + i];
+      double tr[4], tc[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r = rb + i;
+        const double d = md_dist_rd((double)v[i], so[i + 1] - so[i], L.totals[r], pj, rj);
+        tr[i] = (r < n && r >= j) ? d : 0.0;
+        tc[i] = (r < n && r <= j) ? d : 0.0;
+      }
+      const double rs0 = (((rs + tr[0]) + tr[1]) + tr[2]) + tr[3];  // fh = 0: indices lim..lim+3
+      const double cs0 = (((cs + tc[0]) + tc[1]) + tc[2]) + tc[3];
+      const double rsh = __shfl_xor(rs0, 32, kWave), csh = __shfl_xor(cs0, 32, kWave);
+      rs = (((rsh + tr[0]) + tr[1]) + tr[2]) + tr[3];  // fh = 1: indices lim+4..lim+7
+      cs = (((csh + tc[0]) + tc[1]) + tc[2]) + tc[3];
+    }
+    // the fh = 1 lanes hold the finished sums of their columns
+    const double row = 0.0 + rs, col = 0.0 + cs;
+    const double tot = (row + col) / (double)n;  // (row + col) / n
+    if (fh == 1 && jv) {
+      if (totals_out) totals_out[s0 + j] = tot;
+      best = tot;
+      idx = j;
+    }
+    // P6: lowest index of the minimum over the wave's columns
+    SPX_STAMP2(6, -1);
+    // (the wave's minimum by DPP, then the first lane that holds it: lanes 32..63 carry
+    // columns in ascending order, the others +inf, and a total is never NaN)
+    const double least = wave_min_dpp(best);
+    idx = wid * 32 + (__ffsll((unsigned long long)__ballot(best == least)) - 1 - 32);
+    best = least;
+  }
+  if (two) {  // uniform: wave 1's minimum joins wave 0's (every index of wave 1 is the higher one)
+    if (wid == 1 && lane == 0) {
+      L.red[2] = __double_as_longlong(best);
+      L.red[3] = idx;
+    }
+    lds_barrier();  // every wave
+    if (wid == 0) {
+      const double t2 = __longlong_as_double(L.red[2]);
+      if (t2 < best) { best = t2; idx = (int)L.red[3]; }
+    }
+  }
+  if (wid == 0 && lane == 0) rep[c] = s0 + idx;
+  SPX_STAMP2(7, 7);
+}
+
+// hook() runs right after the barrier that opens P4 (every wave calls it, no barrier inside):
+// the fused pass's persistent loop lets its prefetching wave fetch the next cluster's header
+// there, beside the waves that compute.
 template <int BLOCK, int UMAX, int KWMAX, class Hook = MedoidNoHook>
 __device__ __forceinline__ void medoid_tail(MedoidRegSmem<BLOCK, UMAX, KWMAX>& L, int n, int KW, int64_t s0,
                                             int64_t c, int64_t* rep, double* totals_out,
@@ -256,62 +400,20 @@ __device__ __forceinline__ void medoid_tail(MedoidRegSmem<BLOCK, UMAX, KWMAX>& L
   }
   __syncthreads();
   SPX_STAMP2(4, -1);
-  if constexpr (!std::is_same<Hook, MedoidNoHook>::value) hook(0);
-
-  auto row_start = [&](int i) { return i * n - (i * (i - 1)) / 2; };
-  // the matrix cores for the register kernel's P4; the wide kernel (up to 95 row words,
-  // 128 VGPRs) keeps the AND + popcount pairs: there the sequential MFMA chain measured
-  // slower (600-peak spectra, medoid_shapes: 1.12 -> 1.37 ms)
-  // and only for clusters of more than SPX_MD_MFMA_NMIN spectra: below, one wave holds
-  // the one 32 x 32 tile and its epilogue while the pairs spread over the whole workgroup
-  // (stamps, configs[4]: P4 n 41-50 14.4k -> 11.7k cycles, n 11-25 5.7k -> 8.7k)
-  bool mfma_p4 = false;
-  if constexpr (BLOCK == MD_BLOCK) mfma_p4 = n > SPX_MD_MFMA_NMIN;  // uniform
-  if (mfma_p4) {
-  // P4 on the matrix cores: c_ij = |B_i ∩ B_j| = the Gram of the 0/1 rows, one
-  // 32 x 32 tile per wave -- (0,0) for n <= 32; (0,0), (0,1), (1,1) for n <= 64 --
-  // one v_mfma_f32_32x32x64_f8f6f4 per 64-bin row word (FP4 0/1 operands at unit
-  // scale: the f32 sums of <= 2^24 ones are the integer counts), then
-  // d_ij = 1 - c_ij / min(p_i, p_j) into the packed upper triangle
-  {
-    const int fr = lane & 31, fh = lane >> 5;
-    const int ntile = n > 32 ? 3 : 1;
-    const bool work = wid < ntile;  // wave-uniform
-    const int ta = wid == 2 ? 1 : 0, tb = wid == 0 ? 0 : 1;
-    md_f32x16 acc;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
-    if (work) {
-      const int ra = ta * 32 + fr, rb = tb * 32 + fr;
-      const unsigned long long* pa = L.u.a.rows + (ra < n ? ra : 0) * KW;
-      const unsigned long long* pb = L.u.a.rows + (rb < n ? rb : 0) * KW;
-      const unsigned long long ma = ra < n ? ~0ull : 0ull, mb = rb < n ? ~0ull : 0ull;
-      unsigned long long wa = pa[0] & ma, wb = pb[0] & mb;  // one word ahead
-      for (int w = 0; w < KW; ++w) {
-        const int wn = w + 1 < KW ? w + 1 : w;
-        const unsigned long long na = pa[wn] & ma, nb = pb[wn] & mb;
-        acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(md_frag4(wa, fh), md_frag4(wb, fh), acc, 4, 4, 0, 0,
-                                                              0, 0);
-        wa = na;
-        wb = nb;
-      }
-    }
-    __syncthreads();  // rows dead: the distance matrix takes their place
-    if (work) {
-      // C/D layout (32x32): col = lane & 31, row = (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)
-      const int j = tb * 32 + fr;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int i = ta * 32 + (q & 3) + 8 * (q >> 2) + 4 * fh;
-        if (i <= j && j < n) {
-          const uint32_t cnt = (uint32_t)acc[q];
-          L.u.d[row_start(i) + j - i] =
-              md_dist_r(cnt, L.soff[i + 1] - L.soff[i], L.totals[i], L.soff[j + 1] - L.soff[j], L.totals[j]);
-        }
-      }
+  if constexpr (!std::is_same<Hook, MedoidNoHook>::value) hook();
+  if constexpr (BLOCK == MD_BLOCK) {
+    if (SPX_MD_MFMA_NMIN <= 1 || n > SPX_MD_MFMA_NMIN) {  // uniform
+      medoid_tail_regs<BLOCK, UMAX, KWMAX>(L, n, KW, s0, c, rep, totals_out);
+      return;
     }
   }
-  } else {
+
+  auto row_start = [&](int i) { return i * n - (i * (i - 1)) / 2; };
+  // The LDS tail: the wide kernel (up to 95 row words, 128 VGPRs) keeps the AND + popcount
+  // pairs -- there the sequential MFMA chain measured slower (600-peak spectra,
+  // medoid_shapes: 1.12 -> 1.37 ms) -- and so do the 256-thread kernels' clusters of at
+  // most SPX_MD_MFMA_NMIN spectra, if that threshold is above 1.
+  {
     // P4: every pair i <= j of the row-major upper triangle (row i starts at
     // i*n - i*(i-1)/2; recovered by a float sqrt + integer fix-up); counts in
     // registers until the rows are dead
@@ -350,7 +452,6 @@ __device__ __forceinline__ void medoid_tail(MedoidRegSmem<BLOCK, UMAX, KWMAX>& L
   __syncthreads();
   // D(a, b) of the reference's dense matrix: the upper triangle incl. the
   // diagonal, zeros below (most_similar_representative.py:91-93)
-  if constexpr (!std::is_same<Hook, MedoidNoHook>::value) hook(1);
 
   SPX_STAMP2(5, 6);
   // P5: totals, one lane per spectrum (n <= 64): wave 0 sums row i, wave 1 column i, each
