@@ -23,6 +23,8 @@
  *   spx_wire_pack / spx_wire_unpack  (9-byte consensus peaks for the multi-GPU gather to rank 0)
  *   spx_parse_mgf_text  (no reference counterpart: the number parsing of the MGF readers,
  *                       binning.py:122-167 and the pyteomics-shaped one, moved to the device)
+ *   spx_format_peaks  (its counterpart: the writers' peak lines, binning.py:234-245,
+ *                       formatted on the device; spx_mgf_splice_records writes them out)
  *   spx_copy_h2d / spx_copy_d2h  (host transfers of pageable batches: the reference
  *                       holds its spectra in host memory, binning.py:122-167)
  *
@@ -313,6 +315,46 @@ int spx_parse_mgf_text(const void *text, int64_t text_len, const int64_t *rec_be
                        const int64_t *spec_off, int64_t n_records, int64_t n_peaks, int32_t general, double *mz,
                        double *inten, double *prec_mz, int32_t *charge, double *rt, int32_t *flags,
                        int32_t *rec_status, void *stream);
+
+/* ---- device-side MGF emit: the peak lines of the three CLIs' writers formatted in HBM
+ *      (DESIGN.md section 6), the counterpart of spx_parse_mgf_text.  Floats are Python's
+ *      repr(): the shortest decimal that reads back as the same double ("nan", "inf",
+ *      "-inf"; 1e-4 <= |x| < 1e16 positional, else d.ddde+XX), at most 24 bytes. ---- */
+
+/* bytes of workspace for n_segments segments over at most n_peaks peaks */
+size_t spx_format_peaks_workspace_size(int64_t n_segments, int64_t n_peaks);
+
+/* Segment i is peaks [seg_begin[i], seg_end[i]) of mz / inten (device, n_peaks entries).
+ * Its text is one line "repr(mz) ' ' repr(inten) '\n'" per peak, in order; with
+ * skip_nan_inten != 0 a peak whose intensity is NaN produces no line (binning.py:242).
+ * Segments may overlap and come in any order (the medoid CLI's chosen spectra).
+ * Blocks are dense and in segment order: segment i is text[text_off[i] .. text_off[i+1]).
+ * text_capacity >= 50 * (peaks covered) always suffices (24 + 1 + 24 + 1).
+ * flags (device int32[1], zeroed by the caller): bit0 = text_capacity too small (text_off
+ * is still complete -- text_off[n_segments] is the capacity needed -- and no text is
+ * written), bit1 = a segment range outside [0, n_peaks] or reversed (it is emitted as
+ * empty).  Nothing is ever written outside text[0, text_capacity).
+ * Returns SPX_EINVAL for null arrays, negative sizes or a workspace smaller than the query. */
+int spx_format_peaks(const double *mz, const double *inten, int64_t n_peaks,
+                     const int64_t *seg_begin, const int64_t *seg_end, int64_t n_segments,
+                     int32_t skip_nan_inten, uint8_t *text, int64_t text_capacity,
+                     int64_t *text_off /* [n_segments + 1] */, int32_t *flags,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
+/* HOST functions (no device work; like spx_copy_h2d / spx_copy_d2h they use host threads).
+ * spx_repr_f64: Python's repr of x into out (room for 24 bytes, no terminator); returns the
+ * length.  The digit arithmetic is the one the format kernel runs (csrc/repr_core.hpp).
+ * spx_mgf_splice_records: the record writer of spx_mgf.h (same path, append, style 0/1/2,
+ * '\n'-joined titles, flags, prec, charge, rt, threads) over peak lines that are already
+ * text: record c's block is text[text_off[c] .. text_off[c+1]) (host arrays, e.g.
+ * spx_format_peaks' outputs copied back).  It formats the record headers and END IONS,
+ * copies the blocks verbatim and writes in order.  Arguments are checked before the file
+ * is opened; SPX_EINVAL on a bad one or an I/O error. */
+int spx_repr_f64(double x, char *out);
+int spx_mgf_splice_records(const char *path, int32_t append, int32_t style, int64_t n_records,
+                           const char *titles, const int32_t *flags, const double *prec,
+                           const int64_t *charge, const double *rt, const int64_t *text_off,
+                           const uint8_t *text, int32_t threads);
 
 int spx_abi_version(void);
 const char *spx_last_error(void); /* thread-local text of the last failure */

@@ -68,6 +68,7 @@ EXPORTED = ["spx_bin_mean_workspace_size", "spx_bin_mean", "spx_bin_mean_stage",
             "spx_medoid_workspace_size", "spx_medoid_needs_large_path", "spx_medoid", "spx_bin_mean_medoid", "spx_bin_mean_medoid_stage", "spx_xcorr_distance", "spx_binned_cosine_workspace_size", "spx_binned_cosine", "spx_best_score",
             "spx_compact_peaks", "spx_wire_pack", "spx_wire_unpack", "spx_copy_h2d", "spx_copy_d2h",
             "spx_parse_mgf_text",
+            "spx_format_peaks_workspace_size", "spx_format_peaks", "spx_repr_f64", "spx_mgf_splice_records",
             "spx_abi_version", "spx_last_error", "spx_profile_enable", "spx_profile_read",
             "spx_medoid_gram_operand_bits"]
 
@@ -155,9 +156,16 @@ def lib():
                            ("spx_profile_enable", [_i32]), ("spx_profile_read", [ctypes.c_char_p, _p, _p]),
                            ("spx_medoid_gram_operand_bits", []),
                            ("spx_parse_mgf_text",
-                            [_p, _i64, _p, _p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p])):
+                            [_p, _i64, _p, _p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
+                           ("spx_format_peaks_workspace_size", [_i64, _i64]),
+                           ("spx_format_peaks", [_p, _p, _i64, _p, _p, _i64, _i32, _p, _i64, _p, _p, _p, _sz, _p]),
+                           ("spx_repr_f64", [_dbl, ctypes.c_char_p]),
+                           ("spx_mgf_splice_records",
+                            [ctypes.c_char_p, _i32, _i32, _i64, ctypes.c_char_p, _p, _p, _p, _p, _p, _p, _i32])):
         if hasattr(L, name):
             getattr(L, name).argtypes = argtypes
+    if hasattr(L, "spx_format_peaks_workspace_size"):
+        L.spx_format_peaks_workspace_size.restype = _sz
     if L.spx_abi_version() != SPX_ABI_VERSION:
         raise RuntimeError(f"libspecpride_hip ABI {L.spx_abi_version()} != {SPX_ABI_VERSION}")
     _lib = L

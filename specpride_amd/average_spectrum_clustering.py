@@ -189,6 +189,13 @@ def _native_pass(fname, get_cluster=get_cluster_id, get_pepmass=naive_average_ma
     """process_maracluster_mgf's device pass over the native parse: (run ids, host
     result with the precursor fields computed on the device), or None when the
     helpers are custom callables or the file is outside the native subset."""
+    got = _native_device_pass(fname, get_cluster, get_pepmass, get_rt, **kwargs)
+    return None if got is None else (got[0], got[1].to_host())
+
+
+def _native_device_pass(fname, get_cluster=get_cluster_id, get_pepmass=naive_average_mass_and_charge,
+                        get_rt=median_rt, **kwargs):
+    """:func:`_native_pass` with the result left on the device (engine.PeaksResult)."""
     pm_mode = {lower_median_mass: "lower_median", naive_average_mass_and_charge: "naive_average",
                neutral_average_mass_and_charge: "neutral_average"}.get(get_pepmass)
     rt_mode = {median_rt: "median", lower_median_mass_rt: "mass_lower_median"}.get(get_rt)
@@ -206,7 +213,7 @@ def _native_pass(fname, get_cluster=get_cluster_id, get_pepmass=naive_average_ma
         ids, batch = native[0], engine.DeviceBatch.from_host(native[1])
     r = engine.gap_average(batch, kwargs.get("mz_accuracy", DIFF_THRESH),
                            kwargs.get("dyn_range", DYN_RANGE), kwargs.get("min_fraction", MIN_FRACTION),
-                           pepmass=pm_mode, rt=rt_mode).to_host()
+                           pepmass=pm_mode, rt=rt_mode)
     return ids, r
 
 
@@ -273,6 +280,14 @@ def main(argv=None):
                                                 **kwargs)], args.output, file_mode=mode)
     elif args.encodedclusters:
         def single():
+            from . import device_emit, mgf_native
+
+            if args.output is not None and device_emit.enabled():  # opt-in: peak lines formatted on the device
+                got = _native_device_pass(args.input, get_pepmass=get_pepmass, get_rt=get_rt, **kwargs)
+                if got is not None:
+                    device_emit.write_consensus(args.output, mgf_native.STYLE_GAP_AVERAGE, got[0], got[1],
+                                                _raise_for, append=mode == "a")
+                    return
             native = _native_pass(args.input, get_pepmass=get_pepmass, get_rt=get_rt, **kwargs) \
                 if args.output is not None else None
             if native is not None:  # native ingest -> one device pass -> native writer

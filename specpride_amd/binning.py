@@ -53,6 +53,14 @@ def eprint(*args, **kwargs):
 MIXED_CHARGE_MSG = "Not all precursor charges in cluster are equal"
 
 
+def _raise_for(status):
+    """The reference's error for a cluster the engine reports as failed."""
+    if status == engine.STATUS_MIXED_CHARGE:
+        raise AssertionError(MIXED_CHARGE_MSG)
+    # empty cluster: the reference fails on charges[0]
+    raise IndexError("list index out of range")
+
+
 class RepresentativeSpectrumCreator:
     """Bin-mean consensus creator (binning.py:19)."""
 
@@ -158,10 +166,7 @@ class RepresentativeSpectrumCreator:
                               staged=engine.packed_readback(batch)).to_host()
         bad = np.flatnonzero(res["status"] != engine.STATUS_OK)
         if len(bad):
-            if res["status"][bad[0]] == engine.STATUS_MIXED_CHARGE:
-                raise AssertionError(MIXED_CHARGE_MSG)
-            # empty cluster: the reference fails on charges[0]
-            raise IndexError("list index out of range")
+            _raise_for(res["status"][bad[0]])
         return res
 
     def _combine_csr(self, csr, clusters, minimum=100, maximum=2000, binsize=0.02, apply_peak_quorum=True):
@@ -262,13 +267,20 @@ def _main_mgf(mgf_file, out, verbose):
 
     rsc = RepresentativeSpectrumCreator(verbose=verbose)
     print("Reading spectra...")
-    from . import device_ingest
+    from . import device_emit, device_ingest
+
+    def emit(batch, ids):  # opt-in: the peak lines are formatted on the device
+        device_emit.write_consensus(out, mgf_native.STYLE_BINNING, ids,
+                                    engine.bin_mean(batch, minimum=100, maximum=2000, binsize=0.02), _raise_for)
 
     if device_ingest.enabled():  # opt-in: the MGF text is parsed on the device
         got = device_ingest.load(mgf_file, False, mgf_native.GROUP_BINNING, rsc.device)
         if got is not None:
             batch, meta = got
             print("Clustering...")
+            if device_emit.enabled():
+                emit(batch, meta["ids"])
+                return
             res = rsc._combine_batch(batch, minimum=100, maximum=2000, binsize=0.02)
             mgf_native.write_records(out, mgf_native.STYLE_BINNING, meta["ids"], res["out_off"], res["out_mz"],
                                      res["out_int"], res["prec"], res["charge"])
@@ -277,6 +289,9 @@ def _main_mgf(mgf_file, out, verbose):
     if flat is not None:  # native parse straight to the cluster-segmented CSR, native writer
         ids, csr = flat
         print("Clustering...")
+        if device_emit.enabled():
+            emit(engine.DeviceBatch.from_host(csr, rsc.device), ids)
+            return
         res = rsc._combine_host(csr, minimum=100, maximum=2000, binsize=0.02)
         mgf_native.write_records(out, mgf_native.STYLE_BINNING, ids, res["out_off"], res["out_mz"], res["out_int"],
                                  res["prec"], res["charge"])

@@ -56,7 +56,9 @@
 #include "binned_cosine.hip"
 #include "gap_average.hip"
 #include "medoid.hip"
+#include "mgf_format.hip"
 #include "mgf_parse.hip"
+#include "mgf_splice.hpp"
 #include "fused.hip"
 #include "transfer.hip"
 #include "wire.hip"
@@ -702,6 +704,20 @@ GapWs carve_gap(Carver& w, const spx_csr* csr, const spx_gap_params* params, con
   W.in.tile_off = w.take<long long>((size_t)std::max<int64_t>(gap_giant_tile_slots(csr, info, W.in.tile), 1));
   W.in.part = w.take<char>((size_t)std::max<int64_t>(W.part_cap, 1));
   W.scratch = w.base + w.used;
+  return W;
+}
+
+// ------------------------------------------------------------------- MGF emit
+// spx_format_peaks: the segments' offsets among the peaks covered, and the two passes'
+// per-workgroup sums
+struct FormatWs {
+  int64_t *voff, *seg_part, *text_part;
+};
+FormatWs carve_format(Carver& w, int64_t n_segments) {
+  FormatWs W;
+  W.voff = w.take<int64_t>((size_t)n_segments + 1);
+  W.seg_part = w.take<int64_t>(spx::kFmtSegGrid);
+  W.text_part = w.take<int64_t>(spx::kFmtPeakGrid);
   return W;
 }
 
@@ -1420,6 +1436,62 @@ int spx_parse_mgf_text(const void* text, int64_t text_len, const int64_t* rec_be
   return SPX_LAUNCH(mgf_parse_kernel, dim3(grid), dim3(spx::kMgfBlock), reinterpret_cast<hipStream_t>(stream),
                     static_cast<const uint8_t*>(text), text_len, rec_begin, rec_end, spec_off, n_records, n_peaks,
                     (int)general, mz, inten, prec_mz, charge, rt, flags, rec_status);
+}
+
+// ------------------------------------------------------------ device-side MGF emit
+size_t spx_format_peaks_workspace_size(int64_t n_segments, int64_t n_peaks) {
+  if (n_segments < 0 || n_peaks < 0) return 0;
+  Carver w{nullptr, 0};
+  carve_format(w, n_segments);
+  return w.used;
+}
+
+int spx_format_peaks(const double* mz, const double* inten, int64_t n_peaks, const int64_t* seg_begin,
+                     const int64_t* seg_end, int64_t n_segments, int32_t skip_nan_inten, uint8_t* text,
+                     int64_t text_capacity, int64_t* text_off, int32_t* flags, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+  if (n_peaks < 0 || n_segments < 0 || text_capacity < 0) return fail(SPX_EINVAL, "spx_format_peaks: negative size");
+  if ((n_peaks > 0 && (!mz || !inten)) || (n_segments > 0 && (!seg_begin || !seg_end)) || !text_off || !flags ||
+      (text_capacity > 0 && !text))
+    return fail(SPX_EINVAL, "spx_format_peaks: null argument");
+  if (!workspace || workspace_bytes < spx_format_peaks_workspace_size(n_segments, n_peaks))
+    return fail(SPX_EINVAL, "spx_format_peaks: workspace smaller than spx_format_peaks_workspace_size");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int64_t S = n_segments;
+  if (S == 0) {
+    if (hipMemsetAsync(text_off, 0, sizeof(int64_t), s) != hipSuccess) return check_launch("spx_format_peaks memset");
+    return SPX_SUCCESS;
+  }
+  Carver w{static_cast<char*>(workspace), 0};
+  const FormatWs W = carve_format(w, S);
+  const dim3 blk(spx::kFmtBlock);
+  const dim3 gseg((unsigned)std::min<int64_t>((S + spx::kFmtBlock - 1) / spx::kFmtBlock, spx::kFmtSegGrid));
+  // the peaks covered are known on the device only: the grid follows the array's size
+  const dim3 gpk((unsigned)std::max<int64_t>(
+      1, std::min<int64_t>((n_peaks + 2 * spx::kFmtBlock - 1) / (2 * spx::kFmtBlock), spx::kFmtPeakGrid)));
+  int rc = SPX_LAUNCH(fmt_seg_sum_kernel, gseg, blk, s, seg_begin, seg_end, S, n_peaks, W.seg_part, flags);
+  if (!rc) rc = SPX_LAUNCH(fmt_seg_scan_kernel, gseg, blk, s, seg_begin, seg_end, S, n_peaks, W.seg_part, W.voff);
+  if (!rc) rc = SPX_LAUNCH(fmt_peaks_kernel<false>, gpk, blk, s, mz, inten, seg_begin, W.voff, S, skip_nan_inten, text,
+                           text_capacity, text_off, flags, W.text_part);
+  if (!rc) rc = SPX_LAUNCH(fmt_peaks_kernel<true>, gpk, blk, s, mz, inten, seg_begin, W.voff, S, skip_nan_inten, text,
+                           text_capacity, text_off, flags, W.text_part);
+  if (!rc) rc = SPX_LAUNCH(fmt_seg_fix_kernel, gseg, blk, s, W.voff, S, text_off);
+  return rc;
+}
+
+// ------------------------------------------------------------ host side of the emit
+int spx_repr_f64(double x, char* out) {
+  if (!out) return fail(SPX_EINVAL, "spx_repr_f64: null buffer");
+  return spx_repr::repr_f64(x, out);
+}
+
+int spx_mgf_splice_records(const char* path, int32_t append, int32_t style, int64_t n_records, const char* titles,
+                           const int32_t* flags, const double* prec, const int64_t* charge, const double* rt,
+                           const int64_t* text_off, const uint8_t* text, int32_t threads) {
+  if (spx_splice::write_records(path, append, style, n_records, titles, flags, prec, charge, rt, text_off, text,
+                                threads) != 0)
+    return fail(SPX_EINVAL, "spx_mgf_splice_records: bad argument or I/O error");
+  return SPX_SUCCESS;
 }
 
 }  // extern "C"

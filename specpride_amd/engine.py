@@ -723,3 +723,92 @@ def best_score(cluster_off, score, rank, out: Optional[BestScoreResult] = None, 
     _lib.check(_lib.lib().spx_best_score(ctypes.byref(csr), _ptr(score), _ptr(rank), _ptr(out.best),
                                          _ptr(out.status), _stream_handle(stream)), "spx_best_score")
     return out
+
+
+FORMAT_FLAG_CAPACITY, FORMAT_FLAG_RANGE = 1, 2  # spx_format_peaks' flags bits
+FORMAT_LINE_MAX = 50  # "repr(mz) repr(inten)\n": 24 + 1 + 24 + 1 bytes at most
+
+
+@dataclass
+class FormatResult:
+    """Peak lines formatted on the device: segment i's text is
+    ``text[text_off[i]:text_off[i + 1]]`` (uint8), ``flags`` [1] i32 the
+    FORMAT_FLAG_* bits."""
+    text: object
+    text_off: object
+    flags: object
+    stream: object = None  # the torch stream the kernels were enqueued on
+    ws: object = None
+
+    def to_host(self) -> dict:
+        """dict(text uint8 [text_off[-1]], text_off int64 [S + 1], flags int): the
+        offsets and flags first (small), then the text through ``spx_copy_d2h``.
+        With the capacity flag set no text was written: ``text`` is empty and
+        ``text_off[-1]`` is the capacity the segments need."""
+        import torch
+
+        dev = self.text_off.device
+        with torch.cuda.device(dev):
+            cur = torch.cuda.current_stream(dev)
+            if self.stream is not None:
+                cur.wait_stream(self.stream)
+            text_off = self.text_off.cpu().numpy()
+            flags = int(self.flags.cpu().numpy()[0])
+            n = 0 if flags & FORMAT_FLAG_CAPACITY else int(text_off[-1])
+            text = np.empty(n, np.uint8)
+            if n:
+                _lib.check(_lib.lib().spx_copy_d2h(text.ctypes.data, self.text.data_ptr(), n, cur.cuda_stream),
+                           "spx_copy_d2h")
+        return dict(text=text, text_off=text_off, flags=flags)
+
+
+def format_peaks(mz, inten, seg_begin, seg_end, skip_nan=False, stream=None, capacity: Optional[int] = None,
+                 batch: Optional[DeviceBatch] = None, out: Optional[FormatResult] = None) -> FormatResult:
+    """The MGF peak lines ``repr(mz) repr(inten)\\n`` of the segments
+    ``[seg_begin[i], seg_end[i])`` of the device arrays ``mz`` / ``inten``
+    (``spx_format_peaks``): dense blocks in segment order; segments may overlap, be
+    empty or come in any order.  ``skip_nan``: a peak whose intensity is NaN gets no
+    line (binning.py:242).
+
+    ``capacity`` (bytes of text) defaults to 50 per covered peak, which reads the
+    segments' total length back once; pass it (or ``out``, a previous result to
+    write into) to enqueue without a synchronisation.  ``batch``: take the
+    workspace from the batch's reusable buffers."""
+    import torch
+
+    L = _lib.lib()
+    dev = mz.device
+    P, S = int(mz.numel()), int(seg_begin.numel())
+    if int(inten.numel()) != P or int(seg_end.numel()) != S:
+        raise ValueError("format_peaks: mz/inten and seg_begin/seg_end must pair up")
+    for t, dt in ((mz, torch.float64), (inten, torch.float64), (seg_begin, torch.int64), (seg_end, torch.int64)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise ValueError("format_peaks: contiguous float64 peaks and int64 segments on one device")
+    need = L.spx_format_peaks_workspace_size(S, P)
+    with torch.cuda.device(dev):
+        if out is None:
+            if capacity is None:
+                covered = int((seg_end - seg_begin).clamp(0, max(P, 0)).sum().item()) if S else 0
+                capacity = FORMAT_LINE_MAX * covered
+            out = FormatResult(torch.empty(max(int(capacity), 1), dtype=torch.uint8, device=dev),
+                               torch.empty(S + 1, dtype=torch.int64, device=dev),
+                               torch.zeros(1, dtype=torch.int32, device=dev))
+            capacity = int(capacity)
+        else:
+            if int(out.text_off.numel()) != S + 1:
+                raise ValueError("format_peaks: out.text_off must have one entry per segment plus one")
+            capacity = int(out.text.numel()) if capacity is None else min(int(capacity), int(out.text.numel()))
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+                out.flags.zero_()
+        if batch is not None:
+            ws = batch.workspace("format_peaks", need)
+        elif out.ws is not None and out.ws.numel() >= need:
+            ws = out.ws
+        else:
+            ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+        out.ws = ws
+        out.stream = stream
+        _lib.check(L.spx_format_peaks(_ptr(mz), _ptr(inten), P, _ptr(seg_begin), _ptr(seg_end), S, int(bool(skip_nan)),
+                                      _ptr(out.text), capacity, _ptr(out.text_off), _ptr(out.flags), _ptr(ws),
+                                      ws.numel(), _stream_handle(stream)), "spx_format_peaks")
+    return out
