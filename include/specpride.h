@@ -17,6 +17,9 @@
  *   spx_xcorr_distance <- src/most_similar_representative.py:13-19 distance() per pair
  *   spx_binned_cosine  <- src/benchmark.py:10-38  bin_proc / cos_dist / average_cos_dist
  *                       (representative vs its cluster members)
+ *   spx_cosine_medoid  <- the same cos_dist / average_cos_dist with every member as the
+ *                       representative in turn: the member most similar to the rest
+ *                       (literature.md's "most similar spectrum" by binned cosine)
  *   spx_best_score   <- src/best_spectrum.py:67-100  get_best_representative
  *                       (called per cluster from best_spectrum():170-174)
  *   spx_compact_peaks   (packing helper for the shims' output writers)
@@ -243,6 +246,28 @@ size_t spx_binned_cosine_workspace_size(int64_t n_clusters, int64_t max_rep_peak
 int spx_binned_cosine(const spx_csr *csr, const int64_t *rep_off, const double *rep_mz, const double *rep_inten,
                       const spx_cosine_params *params, double *cos_out, double *avg_out, int32_t *status,
                       int64_t max_rep_peaks, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- cosine medoid: per cluster, score[i] = average_cos_dist(member_i, members)
+ *      (benchmark.py:31-38: the sequential sum of cos_dist over the members in file
+ *      order, the self pair included, divided by n) and rep = the first member with the
+ *      maximal score (replaced only on >, so a NaN never replaces anything).  Every pair
+ *      keeps cos_dist's rules (the cut at max(last m/z of the two), numpy's edges, scipy's
+ *      on-edge shift, 0.0 for a zero norm).  S(i,j) and S(j,i) have the same bits, and
+ *      members with equal peaks tie bit for bit (the lower index wins).
+ *      rep [n_clusters]: global spectrum index, -1 if none; score [n_spectra], nullable;
+ *      status [n_clusters]: SPX_OK (an empty cluster: rep -1), SPX_EMPTY if a member has
+ *      no peaks (the reference's mz[-1] raises IndexError; rep -1, NaN scores),
+ *      SPX_UNRESOLVED (rep -1, NaN scores) outside the limits: an m/z >= ~1.07e7 (bin
+ *      index 2^31 - 16), a last m/z that is NaN, infinite or at most mz_space / 2 (the
+ *      reference cannot build its edges), non-finite intensity sums.
+ *      Clusters of <= 64 members and <= 11,264 distinct (spectrum, bin) runs are scored
+ *      from LDS; larger ones from the workspace (any size).  info->max_cluster_peaks and
+ *      max_cluster_spectra must be upper bounds.  Stages every spectrum's binned runs in
+ *      the workspace (28 B per peak). */
+size_t spx_cosine_medoid_workspace_size(const spx_csr *csr, const spx_batch_info *info);
+int spx_cosine_medoid(const spx_csr *csr, const spx_cosine_params *params, const spx_batch_info *info,
+                      int64_t *rep /* [C] global spectrum index; -1 none */, double *score /* [S], nullable */,
+                      int32_t *status /* [C] */, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- best spectrum: best_spectrum.get_best_representative(cluster, scores) for every
  *      cluster: scores.idxmax() over the cluster's members (best_spectrum.py:97-100) ---- */

@@ -65,7 +65,8 @@ class SpxCosineParams(ctypes.Structure):
 
 # every symbol include/specpride.h declares (checked by tests/test_host.py)
 EXPORTED = ["spx_bin_mean_workspace_size", "spx_bin_mean", "spx_bin_mean_stage", "spx_gap_average_workspace_size", "spx_gap_average",
-            "spx_medoid_workspace_size", "spx_medoid_needs_large_path", "spx_medoid", "spx_bin_mean_medoid", "spx_bin_mean_medoid_stage", "spx_xcorr_distance", "spx_binned_cosine_workspace_size", "spx_binned_cosine", "spx_best_score",
+            "spx_medoid_workspace_size", "spx_medoid_needs_large_path", "spx_medoid", "spx_bin_mean_medoid", "spx_bin_mean_medoid_stage", "spx_xcorr_distance", "spx_binned_cosine_workspace_size", "spx_binned_cosine",
+            "spx_cosine_medoid_workspace_size", "spx_cosine_medoid", "spx_best_score",
             "spx_compact_peaks", "spx_wire_pack", "spx_wire_unpack", "spx_copy_h2d", "spx_copy_d2h",
             "spx_parse_mgf_text",
             "spx_format_peaks_workspace_size", "spx_format_peaks", "spx_repr_f64", "spx_mgf_splice_records",
@@ -146,6 +147,9 @@ def lib():
     L.spx_binned_cosine_workspace_size.restype = _sz
     L.spx_binned_cosine_workspace_size.argtypes = [_i64, _i64]
     L.spx_binned_cosine.argtypes = [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _sz, _p]
+    L.spx_cosine_medoid_workspace_size.restype = _sz
+    L.spx_cosine_medoid_workspace_size.argtypes = [_p, _p]
+    L.spx_cosine_medoid.argtypes = [_p, _p, _p, _p, _p, _p, _p, _sz, _p]
     L.spx_best_score.argtypes = [_p, _p, _p, _p, _p, _p]
     L.spx_copy_h2d.argtypes = [_p, _p, _sz, _p]
     L.spx_copy_d2h.argtypes = [_p, _p, _sz, _p]

@@ -4,7 +4,8 @@ cosine, benchmark.py:7-38) on the MI355X engine (``spx_binned_cosine``).
 Same names and argument meanings as the reference: spectra are objects with
 ``.mz`` and ``.intensity`` arrays (spectrum_utils ``MsmsSpectrum`` or anything
 alike).  ``cos_dist`` / ``average_cos_dist`` evaluate one representative;
-``average_cos_dist_batch`` evaluates every cluster of a file in one device pass.
+``average_cos_dist_batch`` evaluates every cluster of a file in one device pass;
+``most_similar_by_cosine`` picks each cluster's most similar member (``spx_cosine_medoid``).
 An empty spectrum raises IndexError, as the reference's ``mz[-1]`` does.
 ``fraction_of_by`` (spectrum_utils peptide annotation) is outside the engine's
 scope.
@@ -50,6 +51,25 @@ def average_cos_dist_batch(representatives, clusters, mz_space=mz_space, device=
         if st != engine.STATUS_OK:
             raise RuntimeError(f"cluster {c}: binned cosine unresolved (status {st})")
     return avg[:csr.n_clusters], [cos[csr.cluster_off[c]:csr.cluster_off[c + 1]] for c in range(csr.n_clusters)]
+
+
+def most_similar_by_cosine(clusters, mz_space=mz_space, device="cuda"):
+    """For every cluster (a list of spectrum objects) the index of the member with the
+    highest ``average_cos_dist(member, cluster)`` -- the first one among equals -- and
+    every member's average, from ONE engine call.  Returns (indices: list of int, -1 for
+    an empty cluster; scores: list of per-cluster arrays)."""
+    csr = SpectraCSR.from_clusters([[{"m/z array": _arrays(s)[0], "intensity array": _arrays(s)[1]} for s in cl]
+                                    for cl in clusters])
+    batch = engine.DeviceBatch.from_host(csr, device=device)
+    rep, score, status = engine.cosine_medoid(batch, mz_space=mz_space, with_scores=True).to_host()
+    indices = []
+    for c, st in enumerate(status[:csr.n_clusters]):
+        if st == engine.STATUS_EMPTY:
+            raise IndexError("index -1 is out of bounds for axis 0 with size 0")  # benchmark.py:20 mz[-1]
+        if st != engine.STATUS_OK:
+            raise RuntimeError(f"cluster {c}: cosine medoid unresolved (status {st})")
+        indices.append(int(rep[c] - csr.cluster_off[c]) if rep[c] >= 0 else -1)
+    return indices, [score[csr.cluster_off[c]:csr.cluster_off[c + 1]] for c in range(csr.n_clusters)]
 
 
 def cos_dist(representative_spectrum, cluster_member):

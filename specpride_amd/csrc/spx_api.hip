@@ -54,6 +54,7 @@
 #include "bin_mean_split.hip"
 #include "bin_mean_wide.hip"
 #include "binned_cosine.hip"
+#include "cosine_medoid.hip"
 #include "gap_average.hip"
 #include "medoid.hip"
 #include "mgf_format.hip"
@@ -962,6 +963,45 @@ CosineWs carve_cosine(Carver& w, int64_t n_clusters) {
   return W;
 }
 
+// ------------------------------------------------------------ cosine medoid
+spx::CosMedWs carve_cosine_medoid(Carver& w, int64_t n_clusters, int64_t n_spectra, int64_t n_peaks) {
+  const size_t P = (size_t)std::max<int64_t>(n_peaks, 1), S = (size_t)std::max<int64_t>(n_spectra, 1);
+  spx::CosMedWs W;
+  W.rb = w.take<int32_t>(P);
+  W.rA = w.take<double>(P);
+  W.rE = w.take<double>(P);
+  W.rA2 = w.take<double>(P);
+  W.nr = w.take<int32_t>(S);
+  W.L = w.take<int32_t>(S);
+  W.nE = w.take<int32_t>(S);
+  W.flag = w.take<int32_t>(S);
+  W.tot2 = w.take<double>(S);
+  W.score = w.take<double>(S);
+  W.n_def = w.take<int32_t>(1);
+  W.def = w.take<int32_t>((size_t)std::max<int64_t>(n_clusters, 1));
+  return W;
+}
+
+// np.arange(-s/2, stop, s): e0 = start, e1 = start + s, e_i = start + i * (e1 - e0)
+// (numpy DOUBLE_fill); scipy's on-edge rounding keeps int(-log10(min edge gap)) + 6 decimals
+spx::CosParams cosine_params(double mz_space) {
+  spx::CosParams P;
+  P.s = mz_space;
+  P.start = -mz_space / 2.0;
+  P.e1 = P.start + P.s;
+  P.d = P.e1 - P.start;
+  P.inv_d = 1.0 / P.d;
+  const int dec = (int)(-std::log10(std::min(P.d, P.s))) + 6;
+  P.p10 = std::pow(10.0, (double)dec);
+  return P;
+}
+
+// runs the LDS image of cosine_medoid_pairs_kernel holds for this batch
+int cosine_medoid_rcap(const spx_batch_info* info) {
+  const int64_t r = std::max<int64_t>(64, std::min<int64_t>(info->max_cluster_peaks, spx::CM_LDS_RUNS));
+  return (int)((r + 63) & ~int64_t(63));
+}
+
 }  // namespace
 
 extern "C" {
@@ -1319,6 +1359,55 @@ int spx_binned_cosine(const spx_csr* csr, const int64_t* rep_off, const double* 
   return SPX_LAUNCH(binned_cosine_global_kernel, dim3((unsigned)fallback_grid(C)), dim3(spx::CS_BLOCK), s, view(csr), P,
                     rep_off, rep_mz, rep_inten, cos_out, avg_out, status, W.def, W.n_def, W.scratch,
                     (int)std::min<int64_t>(max_rep_peaks, INT32_MAX - 1));
+}
+
+// ------------------------------------------------------------ cosine medoid
+size_t spx_cosine_medoid_workspace_size(const spx_csr* csr, const spx_batch_info* info) {
+  if (!csr || !info || csr->n_clusters < 0 || csr->n_spectra < 0 || csr->n_peaks < 0) return 0;
+  Carver w{nullptr, 0};
+  carve_cosine_medoid(w, csr->n_clusters, csr->n_spectra, csr->n_peaks);
+  return w.used;
+}
+
+int spx_cosine_medoid(const spx_csr* csr, const spx_cosine_params* params, const spx_batch_info* info, int64_t* rep,
+                      double* score, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!csr_ok(csr) || !params || !info || !rep || !status)
+    return fail(SPX_EINVAL, "spx_cosine_medoid: null argument");
+  if (!(params->mz_space > 0)) return fail(SPX_EINVAL, "spx_cosine_medoid: mz_space must be > 0");
+  const int64_t C = csr->n_clusters, S = csr->n_spectra;
+  if (C > INT32_MAX) return fail(SPX_EINVAL, "spx_cosine_medoid: too many clusters");
+  const size_t need = spx_cosine_medoid_workspace_size(csr, info);
+  if (need == 0 || !workspace || workspace_bytes < need) return fail(SPX_ENOSPACE, "spx_cosine_medoid: workspace too small");
+  if (C == 0) return SPX_SUCCESS;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  Carver w{static_cast<char*>(workspace), 0};
+  const spx::CosMedWs W = carve_cosine_medoid(w, C, S, csr->n_peaks);
+  const spx::CosParams P = cosine_params(params->mz_space);
+  const spx::CsrView V = view(csr);
+  if (hipMemsetAsync(W.n_def, 0, sizeof(int32_t), s) != hipSuccess) return check_launch("spx_cosine_medoid memset");
+  if (S > 0) {
+    const int64_t waves = spx::CM_BLOCK / spx::kWave;
+    const unsigned g1 = (unsigned)std::max<int64_t>(1, std::min<int64_t>((S + waves - 1) / waves, 16384));
+    if (int rc = SPX_LAUNCH(cosine_medoid_bin_kernel, dim3(g1), dim3(spx::CM_BLOCK), s, V, P, W)) return rc;
+    const unsigned g2 = (unsigned)std::max<int64_t>(1, std::min<int64_t>((S + spx::CM_BLOCK - 1) / spx::CM_BLOCK, 8192));
+    if (int rc = SPX_LAUNCH(cosine_medoid_prefix_kernel, dim3(g2), dim3(spx::CM_BLOCK), s, V, W)) return rc;
+  }
+  const int rcap = cosine_medoid_rcap(info);
+  const size_t lds = spx::cm_lds_bytes(rcap);
+  if (lds > 65536 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(spx::cosine_medoid_pairs_kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return fail(SPX_EHIP, "spx_cosine_medoid: LDS size attribute");
+  hipLaunchKernelGGL(spx::cosine_medoid_pairs_kernel, dim3((unsigned)C), dim3(spx::CM_PAIR_BLOCK), lds, s, V, W, rcap, rep,
+                     score, status);
+  if (int rc = check_launch("cosine_medoid_pairs_kernel")) return rc;
+  // nothing can be deferred when every cluster fits the LDS path by the caller's bounds
+  if (info->max_cluster_spectra <= spx::CM_NCAP && info->max_cluster_peaks <= rcap) return SPX_SUCCESS;
+  double* sc = score ? score : W.score;
+  const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(C, 32));
+  if (int rc = SPX_LAUNCH(cosine_medoid_rows_kernel, dim3(64, gy), dim3(spx::CM_BLOCK), s, V, W, sc)) return rc;
+  const unsigned g4 = (unsigned)std::max<int64_t>(1, std::min<int64_t>((C + spx::CM_BLOCK - 1) / spx::CM_BLOCK, 1024));
+  return SPX_LAUNCH(cosine_medoid_argmax_kernel, dim3(g4), dim3(spx::CM_BLOCK), s, V, W, sc, rep, status);
 }
 
 // --------------------------------------------------------- best spectrum

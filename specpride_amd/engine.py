@@ -694,6 +694,56 @@ def binned_cosine(batch: DeviceBatch, rep_off, rep_mz, rep_int, mz_space=MZ_SPAC
     return out
 
 
+# spx_cosine_medoid's LDS path (csrc/cosine_medoid.hip): clusters of at most
+# COSINE_MEDOID_LDS_MEMBERS spectra and COSINE_MEDOID_LDS_RUNS runs (distinct bins summed
+# over the members, never more than the peaks) are scored from LDS, larger ones from the
+# workspace; COSINE_MEDOID_MAX_MZ bounds every m/z (bin index 2**31 - 16).
+COSINE_MEDOID_LDS_MEMBERS = 64
+COSINE_MEDOID_LDS_RUNS = 11264
+COSINE_MEDOID_MAX_MZ = (2 ** 31 - 16) * MZ_SPACE - MZ_SPACE / 2
+
+
+@dataclass
+class CosineMedoidResult:
+    rep: object     # [C] i64: global spectrum index of the most similar member (-1: none)
+    score: object   # [S] f64 average_cos_dist(member, members), or None
+    status: object  # [C] i32 (STATUS_EMPTY: an empty member; STATUS_UNRESOLVED: outside the limits)
+    stream: object = None
+
+    def to_host(self):
+        import torch
+
+        if self.stream is not None:
+            torch.cuda.current_stream(self.rep.device).wait_stream(self.stream)
+        return (self.rep.cpu().numpy(), None if self.score is None else self.score.cpu().numpy(),
+                self.status.cpu().numpy())
+
+
+def cosine_medoid(batch: DeviceBatch, mz_space=MZ_SPACE, with_scores=False,
+                  out: Optional[CosineMedoidResult] = None, stream=None) -> CosineMedoidResult:
+    """The member of every cluster with the highest average binned cosine to the
+    cluster's members, itself included (benchmark.py:19-38 with every member as the
+    representative in turn; the first maximum wins): ``spx_cosine_medoid``.  ``score``
+    (``with_scores``, or ``out`` with a score tensor) is each member's average."""
+    import torch
+
+    dev = batch.device
+    C, S = batch.n_clusters, batch.n_spectra
+    if out is None:
+        out = CosineMedoidResult(torch.empty(max(C, 1), dtype=torch.int64, device=dev),
+                                 torch.empty(max(S, 1), dtype=torch.float64, device=dev) if with_scores else None,
+                                 torch.empty(max(C, 1), dtype=torch.int32, device=dev))
+    out.stream = stream
+    L = _lib.lib()
+    need = L.spx_cosine_medoid_workspace_size(ctypes.byref(batch.csr), ctypes.byref(batch.info))
+    ws = batch.workspace("cosine_medoid", need)
+    prm = _lib.SpxCosineParams(float(mz_space))
+    _lib.check(L.spx_cosine_medoid(ctypes.byref(batch.csr), ctypes.byref(prm), ctypes.byref(batch.info),
+                                   _ptr(out.rep), _ptr(out.score), _ptr(out.status), _ptr(ws), ws.numel(),
+                                   _stream_handle(stream)), "spx_cosine_medoid")
+    return out
+
+
 @dataclass
 class BestScoreResult:
     best: object    # [C] i64: global spectrum index of the highest-scoring member (-1: none)

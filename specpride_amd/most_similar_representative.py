@@ -21,6 +21,13 @@ Kept from the reference:
   ``MascotGenericFile.store`` formatting is not reproduced: parity is on the
   chosen spectrum and its title).
 
+``-m <method>`` (not in the reference's CLI) chooses how the representative is
+scored: ``xcorr`` (the default: everything above) or ``cosine``, the member with the
+highest average binned cosine to its cluster's members (``benchmark.average_cos_dist``
+with every member as the representative in turn, the first maximum; literature.md's
+"most similar spectrum"), through ``spx_cosine_medoid``.  The cluster scan, the prints
+and the verbatim output are the same; only the chooser differs.
+
 All clusters of a file are scored in ONE device pass.
 """
 from __future__ import annotations
@@ -35,6 +42,8 @@ from .csr import SpectraCSR
 from .mgf import format_charge, read_mgf
 
 TOLERANCE = 0.1  # most_similar_representative.py:15
+METHODS = ("xcorr", "cosine")
+USAGE = "most_similar_representative.py -i <inputfile> -o <outputfile>"
 
 
 def _mz_of(spec):
@@ -113,11 +122,11 @@ def _write_spectra(spectra, path):
                          sp["m/z array"], sp["intensity array"])
 
 
-def representatives(spectra, names):
+def representatives(spectra, names, method="xcorr"):
     """Indices (into ``spectra``) of the representative of every cluster run."""
     runs = [(cl, m) for cl, m in _first_runs(names) if m]
     csr = SpectraCSR.from_clusters([[spectra[i] for i in members] for _cl, members in runs])
-    return _choose(csr, runs)
+    return _choose(csr, runs, method)
 
 
 def _medoid_rep(batch):
@@ -128,22 +137,50 @@ def _medoid_rep(batch):
     return rep
 
 
-def _choose(csr, runs):
-    rep = _medoid_rep(engine.DeviceBatch.from_host(csr))
+def _cosine_rep(batch):
+    """Host ``rep`` of the batch's cosine medoid (``-m cosine``); an empty spectrum
+    fails as the reference's ``mz[-1]`` does (benchmark.py:20)."""
+    rep, _, status = engine.cosine_medoid(batch).to_host()
+    status = status[:batch.n_clusters]
+    if np.any(status == engine.STATUS_EMPTY):
+        raise IndexError("index -1 is out of bounds for axis 0 with size 0")
+    if np.any(status != engine.STATUS_OK):
+        raise RuntimeError("cosine medoid engine could not resolve a cluster (see DESIGN.md limits)")
+    return rep[:batch.n_clusters]
+
+
+def _rep(batch, method):
+    return _cosine_rep(batch) if method == "cosine" else _medoid_rep(batch)
+
+
+def cosine_compute(sub, device="cuda"):
+    """``sharded_cli.medoid``'s ``compute=`` for ``-m cosine``: ``member`` = the chosen
+    index within each cluster (-1: not resolved or an empty member; rank 0 raises)."""
+    import torch
+
+    batch = engine.DeviceBatch.from_host(sub, device)
+    res = engine.cosine_medoid(batch)
+    rep = res.rep[:sub.n_clusters]
+    ok = res.status[:sub.n_clusters] == engine.STATUS_OK
+    return dict(member=torch.where(ok & (rep >= 0), rep - batch.t["cluster_off"][:-1], torch.full_like(rep, -1)))
+
+
+def _choose(csr, runs, method="xcorr"):
+    rep = _rep(engine.DeviceBatch.from_host(csr), method)
     out = []
     for c, (cl, members) in enumerate(runs):
         out.append((cl, members, members[int(rep[c] - csr.cluster_off[c])]))
     return out
 
 
-def _main_native(inputfile, outputfile):
+def _main_native(inputfile, outputfile, method="xcorr"):
     """main() over the native parse: records straight into the CSR, the reference's
     cluster scan done natively (spx_mgf_group mode 2), the chosen records written
     from the flat arrays.  False when the file is outside the native subset or a
     record has no TITLE (the dict path then decides)."""
     from . import device_ingest, ingest, mgf_native
 
-    if device_ingest.enabled() and _main_device(inputfile, outputfile):
+    if device_ingest.enabled() and _main_device(inputfile, outputfile, method):
         return True
     try:
         flat = mgf_native.parse_general(inputfile, group=mgf_native.GROUP_FIRST_RUNS)
@@ -155,14 +192,14 @@ def _main_native(inputfile, outputfile):
     records = np.flatnonzero(key >= 0)  # each id's first run, runs in file order
     sizes = np.bincount(key[records], minlength=len(ids))
     csr = ingest.csr_from_flat(flat, sizes, None if len(records) == len(key) else records)
-    rep = _medoid_rep(engine.DeviceBatch.from_host(csr))
+    rep = _rep(engine.DeviceBatch.from_host(csr), method)
     print("".join(f"{cl}\n{n}\n" for cl, n in zip(ids, sizes.tolist())), end="")
     print(len(ids))
     write_chosen(outputfile, flat, records[rep])
     return True
 
 
-def _main_device(inputfile, outputfile):
+def _main_device(inputfile, outputfile, method="xcorr"):
     """:func:`_main_native` with the MGF text parsed on the device (opt-in,
     ``SPX_DEVICE_INGEST=1``): the same cluster scan, prints and output.  False when
     the file is outside the native subset as a whole (the host paths then decide)."""
@@ -172,7 +209,7 @@ def _main_device(inputfile, outputfile):
     if got is None:
         return False
     batch, meta = got
-    rep = _medoid_rep(batch)
+    rep = _rep(batch, method)
     ids, sizes = meta["ids"], meta["sizes"]
     print("".join(f"{cl}\n{n}\n" for cl, n in zip(ids, sizes.tolist())), end="")
     print(len(ids))
@@ -201,7 +238,7 @@ def write_chosen(outputfile, flat, chosen):
                              flat["rt"][chosen], flags)
 
 
-def _main_dicts(inputfile, outputfile):
+def _main_dicts(inputfile, outputfile, method="xcorr"):
     """main() over the dict reader (``specpride_amd.mgf.read_mgf``): the path for
     input outside the native parser's subset.  Same cluster scan, prints and
     output as :func:`_main_native`; a record without TITLE fails as the
@@ -214,7 +251,7 @@ def _main_dicts(inputfile, outputfile):
             raise AttributeError("'NoneType' object has no attribute 'decode'")
         names.append(title.split(";")[0])
     chosen = []
-    for cl, members, best in representatives(spectra, names):
+    for cl, members, best in representatives(spectra, names, method):
         print(cl)
         print(len(members))
         chosen.append(spectra[best])
@@ -222,34 +259,41 @@ def _main_dicts(inputfile, outputfile):
     _write_spectra(chosen, outputfile)
 
 
-def main_single(inputfile, outputfile):
+def main_single(inputfile, outputfile, method="xcorr"):
     """The single-process CLI body: native ingest, else the dict path (never
     re-enters the torchrun dispatch: the sharded CLI's rank-0 fallback runs this)."""
-    if not _main_native(inputfile, outputfile):
-        _main_dicts(inputfile, outputfile)
+    if not _main_native(inputfile, outputfile, method):
+        _main_dicts(inputfile, outputfile, method)
 
 
 def main(argv):
-    inputfile, outputfile = "", ""
+    inputfile, outputfile, method = "", "", "xcorr"
     try:
-        opts, _args = getopt.getopt(argv, "hi:o:")
+        opts, _args = getopt.getopt(argv, "hi:o:m:")
     except getopt.GetoptError:
-        print("most_similar_representative.py -i <inputfile> -o <outputfile>")
+        print(USAGE)
         sys.exit(2)
     for opt, arg in opts:
         if opt == "-h":
-            print("most_similar_representative.py -i <inputfile> -o <outputfile>")
+            print(USAGE)
             sys.exit()
         elif opt in ("-i",):
             inputfile = arg
         elif opt in ("-o",):
             outputfile = arg
+        elif opt in ("-m",):
+            method = arg
+    if method not in METHODS:
+        print(USAGE)
+        sys.exit(2)
     from . import sharded_cli
 
     if sharded_cli.launched_distributed():  # torchrun: rank-local ingest, one GPU per rank
-        sharded_cli.run_cli(sharded_cli.medoid, lambda: main_single(inputfile, outputfile), inputfile, outputfile)
+        extra = dict(compute=cosine_compute) if method == "cosine" else {}
+        sharded_cli.run_cli(sharded_cli.medoid, lambda: main_single(inputfile, outputfile, method), inputfile,
+                            outputfile, **extra)
         return
-    main_single(inputfile, outputfile)
+    main_single(inputfile, outputfile, method)
 
 
 if __name__ == "__main__":
