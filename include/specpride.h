@@ -283,6 +283,40 @@ int spx_cosine_medoid(const spx_csr *csr, const spx_cosine_params *params, const
 int spx_best_score(const spx_csr *csr, const double *score, const int64_t *rank, int64_t *best, int32_t *status,
                    void *stream);
 
+/* ---- explained b/y intensity: benchmark.fraction_of_by (src/benchmark.py:40-61) for every
+ *      segment of a peak array: the share of a spectrum's remaining intensity that the
+ *      b and y fragment ions of its peptide annotate (DESIGN.md sections 3-5) ---- */
+
+/* What spectrum_utils and pyteomics contribute, as parameters (defaults: the values
+ * in the comments; specpride_amd._lib.default_by_params()). */
+typedef struct spx_by_params {
+  double aa_mass[26];      /* residue mass by letter - 'A' (pyteomics std_aa_mass); NaN = not a residue */
+  double h, o, proton;     /* mass.fast_mass: 1.00782503207, 15.99491461956, 1.00727646677 */
+  double precursor_proton; /* remove_precursor_peak: 1.0072766 */
+  double min_mz, max_mz;   /* set_mz_range: 100, 1400 (both ends kept) */
+  double tol_ppm;          /* precursor and fragment tolerance: 50 */
+} spx_by_params;
+
+/* Segment i is peaks [seg_begin[i], seg_end[i]) of mz / inten (device, n_peaks entries),
+ * as in spx_format_peaks: segments may overlap, be empty and come in any order, so one
+ * call serves a batch's member spectra (spec_off[:-1], spec_off[1:]) and dense consensus
+ * outputs alike.  Its precursor is prec_mz[i] at charge[i], its peptide the bytes
+ * seq[seq_off[i] .. seq_off[i+1]) (upper-case one-letter residues).  Peaks need not be
+ * sorted: wherever the reference's sorted order matters the order is (m/z, index).
+ * fraction[i] = by_current / current (0.0 unless current > 0, so also for a NaN among the
+ * remaining intensities); status[i] = SPX_OK.  A sequence with a byte that is no residue
+ * of params->aa_mass is SPX_OK with 0.0 (parser.fast_valid fails).  SPX_UNRESOLVED with a
+ * NaN fraction: a non-finite m/z or precursor m/z, a sequence longer than 256 residues, a
+ * charge above 64, a segment range outside [0, n_peaks] or reversed, or a negative
+ * sequence range (nothing is read outside mz / inten; seq_off is trusted beyond its sign).
+ * All arrays are device pointers, params is a host struct; no workspace, no allocation,
+ * one launch, asynchronous on stream.  SPX_EINVAL for null arrays or negative sizes. */
+int spx_by_fraction(const double *mz, const double *inten, int64_t n_peaks,
+                    const int64_t *seg_begin, const int64_t *seg_end, int64_t n_segments,
+                    const double *prec_mz, const int32_t *charge /* [n_segments] */,
+                    const uint8_t *seq, const int64_t *seq_off /* [n_segments + 1] */,
+                    const spx_by_params *params, double *fraction, int32_t *status, void *stream);
+
 /* Pack the per-cluster outputs densely: dst[out_off[c] + k] = src[spec_off[cluster_off[c]] + k]
  * for k < count[c]; out_off is the exclusive prefix sum of count (device array [C+1]). */
 int spx_compact_peaks(const spx_csr *csr, const spx_peaks_out *src, const int64_t *out_off,

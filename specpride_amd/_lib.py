@@ -63,10 +63,34 @@ class SpxCosineParams(ctypes.Structure):
     _fields_ = [("mz_space", _dbl)]
 
 
+class SpxByParams(ctypes.Structure):
+    _fields_ = [("aa_mass", _dbl * 26), ("h", _dbl), ("o", _dbl), ("proton", _dbl), ("precursor_proton", _dbl),
+                ("min_mz", _dbl), ("max_mz", _dbl), ("tol_ppm", _dbl)]
+
+
+# pyteomics mass.std_aa_mass (five decimals) and the nist_mass entries mass.fast_mass reads
+STD_AA_MASS = {"G": 57.02146, "A": 71.03711, "S": 87.03203, "P": 97.05276, "V": 99.06841, "T": 101.04768,
+               "C": 103.00919, "L": 113.08406, "I": 113.08406, "N": 114.04293, "D": 115.02694, "Q": 128.05858,
+               "K": 128.09496, "E": 129.04259, "M": 131.04049, "H": 137.05891, "F": 147.06841, "R": 156.10111,
+               "Y": 163.06333, "W": 186.07931}
+
+
+def default_by_params() -> SpxByParams:
+    """spx_by_fraction's parameters at the values fraction_of_by runs with (benchmark.py:47-52,
+    spectrum_utils' precursor proton, pyteomics' masses); a fresh struct, so change it freely."""
+    p = SpxByParams()
+    for k in range(26):
+        p.aa_mass[k] = STD_AA_MASS.get(chr(ord("A") + k), float("nan"))
+    p.h, p.o, p.proton = 1.00782503207, 15.99491461956, 1.00727646677
+    p.precursor_proton = 1.0072766
+    p.min_mz, p.max_mz, p.tol_ppm = 100.0, 1400.0, 50.0
+    return p
+
+
 # every symbol include/specpride.h declares (checked by tests/test_host.py)
 EXPORTED = ["spx_bin_mean_workspace_size", "spx_bin_mean", "spx_bin_mean_stage", "spx_gap_average_workspace_size", "spx_gap_average",
             "spx_medoid_workspace_size", "spx_medoid_needs_large_path", "spx_medoid", "spx_bin_mean_medoid", "spx_bin_mean_medoid_stage", "spx_xcorr_distance", "spx_binned_cosine_workspace_size", "spx_binned_cosine",
-            "spx_cosine_medoid_workspace_size", "spx_cosine_medoid", "spx_best_score",
+            "spx_cosine_medoid_workspace_size", "spx_cosine_medoid", "spx_best_score", "spx_by_fraction",
             "spx_compact_peaks", "spx_wire_pack", "spx_wire_unpack", "spx_copy_h2d", "spx_copy_d2h",
             "spx_parse_mgf_text",
             "spx_format_peaks_workspace_size", "spx_format_peaks", "spx_repr_f64", "spx_mgf_splice_records",
@@ -151,6 +175,7 @@ def lib():
     L.spx_cosine_medoid_workspace_size.argtypes = [_p, _p]
     L.spx_cosine_medoid.argtypes = [_p, _p, _p, _p, _p, _p, _p, _sz, _p]
     L.spx_best_score.argtypes = [_p, _p, _p, _p, _p, _p]
+    L.spx_by_fraction.argtypes = [_p, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p]
     L.spx_copy_h2d.argtypes = [_p, _p, _sz, _p]
     L.spx_copy_d2h.argtypes = [_p, _p, _sz, _p]
     # symbols added in ABI 2's round 4 (bound when present: A/B runs load older builds)

@@ -54,6 +54,7 @@
 #include "bin_mean_split.hip"
 #include "bin_mean_wide.hip"
 #include "binned_cosine.hip"
+#include "by_fraction.hip"
 #include "cosine_medoid.hip"
 #include "gap_average.hip"
 #include "medoid.hip"
@@ -1408,6 +1409,26 @@ int spx_cosine_medoid(const spx_csr* csr, const spx_cosine_params* params, const
   if (int rc = SPX_LAUNCH(cosine_medoid_rows_kernel, dim3(64, gy), dim3(spx::CM_BLOCK), s, V, W, sc)) return rc;
   const unsigned g4 = (unsigned)std::max<int64_t>(1, std::min<int64_t>((C + spx::CM_BLOCK - 1) / spx::CM_BLOCK, 1024));
   return SPX_LAUNCH(cosine_medoid_argmax_kernel, dim3(g4), dim3(spx::CM_BLOCK), s, V, W, sc, rep, status);
+}
+
+// ------------------------------------------------- explained b/y intensity
+int spx_by_fraction(const double* mz, const double* inten, int64_t n_peaks, const int64_t* seg_begin,
+                    const int64_t* seg_end, int64_t n_segments, const double* prec_mz, const int32_t* charge,
+                    const uint8_t* seq, const int64_t* seq_off, const spx_by_params* params, double* fraction,
+                    int32_t* status, void* stream) {
+  static_assert(sizeof(spx::ByParams) == sizeof(spx_by_params), "ByParams mirrors spx_by_params");
+  if (n_peaks < 0 || n_segments < 0) return fail(SPX_EINVAL, "spx_by_fraction: negative size");
+  if (!params || (n_peaks > 0 && (!mz || !inten)) ||
+      (n_segments > 0 && (!seg_begin || !seg_end || !prec_mz || !charge || !seq || !seq_off || !fraction || !status)))
+    return fail(SPX_EINVAL, "spx_by_fraction: null argument");
+  if (n_segments == 0) return SPX_SUCCESS;
+  const int64_t blocks = (n_segments + spx::BY_WAVES - 1) / spx::BY_WAVES;
+  if (blocks > INT32_MAX) return fail(SPX_EINVAL, "spx_by_fraction: too many segments");
+  spx::ByParams P;
+  std::memcpy(&P, params, sizeof(P));
+  return SPX_LAUNCH(by_fraction_kernel, dim3((unsigned)blocks), dim3(spx::BY_WAVES * spx::kWave),
+                    reinterpret_cast<hipStream_t>(stream), mz, inten, n_peaks, seg_begin, seg_end, n_segments, prec_mz,
+                    charge, seq, seq_off, P, fraction, status);
 }
 
 // --------------------------------------------------------- best spectrum

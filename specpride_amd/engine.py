@@ -775,6 +775,58 @@ def best_score(cluster_off, score, rank, out: Optional[BestScoreResult] = None, 
     return out
 
 
+BY_MAX_SEQ, BY_MAX_CHARGE = 256, 64  # spx_by_fraction's limits (csrc/by_fraction.hip)
+
+
+@dataclass
+class ByFractionResult:
+    fraction: object  # [S] f64: by_current / current (NaN where status is STATUS_UNRESOLVED)
+    status: object    # [S] i32: STATUS_OK or STATUS_UNRESOLVED
+
+    def to_host(self):
+        return self.fraction.cpu().numpy(), self.status.cpu().numpy()
+
+
+def by_fraction(mz, inten, seg_begin, seg_end, prec_mz, charge, seq, seq_off, params=None,
+                out: Optional[ByFractionResult] = None, stream=None) -> ByFractionResult:
+    """fraction_of_by (benchmark.py:40-61) for every segment ``[seg_begin[i], seg_end[i])``
+    of the device arrays ``mz`` / ``inten`` in one launch (``spx_by_fraction``): the share
+    of the spectrum's remaining intensity that the b/y ions of its peptide annotate.
+
+    Device tensors: ``prec_mz`` f64 and ``charge`` i32 per segment, ``seq`` uint8 (the
+    peptides' upper-case letters, back to back) with ``seq_off`` i64 [S + 1].  ``params``
+    is a ``_lib.SpxByParams`` (default ``_lib.default_by_params()``).  Segments may
+    overlap and peaks need not be sorted.  No workspace, no synchronisation."""
+    import torch
+
+    dev = mz.device
+    P, S = int(mz.numel()), int(seg_begin.numel())
+    if (int(inten.numel()) != P or int(seg_end.numel()) != S or int(prec_mz.numel()) != S or int(charge.numel()) != S
+            or int(seq_off.numel()) != S + 1):
+        raise ValueError("by_fraction: mz/inten pair up, one seg_begin/seg_end/prec_mz/charge per segment, "
+                         "seq_off one more")
+    for t, dt in ((mz, torch.float64), (inten, torch.float64), (seg_begin, torch.int64), (seg_end, torch.int64),
+                  (prec_mz, torch.float64), (charge, torch.int32), (seq, torch.uint8), (seq_off, torch.int64)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise ValueError("by_fraction: contiguous tensors on one device: float64 peaks and precursors, "
+                             "int64 segments and offsets, int32 charges, uint8 sequences")
+    if params is None:
+        params = _lib.default_by_params()
+    with torch.cuda.device(dev):
+        if out is None:
+            out = ByFractionResult(torch.empty(max(S, 1), dtype=torch.float64, device=dev),
+                                   torch.empty(max(S, 1), dtype=torch.int32, device=dev))
+        elif int(out.fraction.numel()) < S or int(out.status.numel()) < S:
+            raise ValueError("by_fraction: out must hold one fraction and one status per segment")
+        if int(seq.numel()) == 0:
+            seq = torch.zeros(1, dtype=torch.uint8, device=dev)  # every sequence is empty: never read
+        _lib.check(_lib.lib().spx_by_fraction(_ptr(mz) if P else None, _ptr(inten) if P else None, P, _ptr(seg_begin),
+                                              _ptr(seg_end), S, _ptr(prec_mz), _ptr(charge), _ptr(seq), _ptr(seq_off),
+                                              ctypes.byref(params), _ptr(out.fraction), _ptr(out.status),
+                                              _stream_handle(stream)), "spx_by_fraction")
+    return out
+
+
 FORMAT_FLAG_CAPACITY, FORMAT_FLAG_RANGE = 1, 2  # spx_format_peaks' flags bits
 FORMAT_LINE_MAX = 50  # "repr(mz) repr(inten)\n": 24 + 1 + 24 + 1 bytes at most
 
