@@ -241,7 +241,11 @@ typedef struct spx_cosine_params {
  * reference's mz[-1] raises IndexError; NaN outputs).  Representatives of up to
  * 512 peaks are sorted in LDS; longer ones (max_rep_peaks = an upper bound on
  * every representative's length) in a global workspace slice, so any length is
- * evaluated; SPX_UNRESOLVED only if a representative exceeds max_rep_peaks. */
+ * evaluated; SPX_UNRESOLVED only if a representative exceeds max_rep_peaks.
+ * Non-finite intensities follow the reference's dense dot products: a bin that
+ * sums to +-inf inside the pair's cut gives NaN (inf * 0 of the other spectrum)
+ * unless the other spectrum is all zero (0.0); past the cut it is dropped; a
+ * finite value whose square overflows gives 0.0. */
 size_t spx_binned_cosine_workspace_size(int64_t n_clusters, int64_t max_rep_peaks);
 int spx_binned_cosine(const spx_csr *csr, const int64_t *rep_off, const double *rep_mz, const double *rep_inten,
                       const spx_cosine_params *params, double *cos_out, double *avg_out, int32_t *status,

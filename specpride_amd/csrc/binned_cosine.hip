@@ -21,6 +21,12 @@
 //     member's own runs of equal bins (sums in input order; an unsorted member
 //     takes an O(m^2) pass instead)
 //   * average_cos_dist = the sequential mean over the members in order.
+//   * non-finite intensities: the dense np.dot multiplies a bin that sums to +-inf
+//     with the other spectrum's 0.0 (nan), so such a bin inside the cut gives NaN
+//     unless the other spectrum is all zero; the sparse sums would never form that
+//     product, so a pair whose norms are not finite is searched for a run under the
+//     cut that sums to +-inf, on either side (a NaN sum, or a finite square that
+//     overflows, needs no help: nan and 0.0).  Finite spectra pay one compare.
 // Dot products are summed in a different order than BLAS's ddot: values agree
 // with the reference to ~1e-15 relative (the north star asks 1e-5).
 #include "spx_device.hpp"
@@ -73,6 +79,7 @@ struct CosShared {               // LDS of both kernels
   double tmpd[CS_NW + 1];
   int tmp[CS_NW + 1];
   int nruns;
+  int inf_lo;  // the first run of a bin >= 0 whose sum is +-inf (nruns if none)
 };
 
 struct CosSmem {
@@ -131,6 +138,7 @@ __device__ bool cos_body(const CsrView& v, const CosParams& P, const CosState& S
   const int64_t r0 = rep_off[c];
   const int R = (int)(rep_off[c + 1] - r0);
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double inf = __longlong_as_double(0x7ff0000000000000ll);
   if (n == 0) {  // average_cos_dist of no members (benchmark.py:36-38)
     if (tid == 0) { avg_out[c] = 0.0; status[c] = kOk; }
     return true;
@@ -192,7 +200,7 @@ __device__ bool cos_body(const CsrView& v, const CosParams& P, const CosState& S
         ++id;
       }
     }
-    if (tid == 0) { L.nruns = nr; S.rs[nr] = R; }
+    if (tid == 0) { L.nruns = nr; L.inf_lo = nr; S.rs[nr] = R; }
     __syncthreads();
     const int PR = (nr + CS_BLOCK - 1) / CS_BLOCK;
     double sq = 0.0;
@@ -210,6 +218,25 @@ __device__ bool cos_body(const CsrView& v, const CosParams& P, const CosState& S
       }
     }
     if (tid == 0) S.rA2[nr] = tot;
+    // a non-finite square: the scan's exclusive value (inclusive - own) is inf - inf at
+    // and after it, so the prefix is redone one by one; and a run whose SUM is +-inf
+    // is an infinite entry of the dense vector (see the member loop's result)
+    if (!(fabs(tot) < inf)) {  // (uniform; no finite spectrum comes here)
+      __syncthreads();
+      if (tid == 0) {
+        double acc = 0.0;
+        int lo = nr;
+        for (int r = 0; r < nr; ++r) {
+          S.rA2[r] = acc;
+          if (S.rb[r] >= 0) {
+            acc += S.rA[r] * S.rA[r];
+            if (lo == nr && fabs(S.rA[r]) == inf) lo = r;
+          }
+        }
+        S.rA2[nr] = acc;
+        L.inf_lo = lo;
+      }
+    }
     // bucket t: the first run with a bin >= t << CS_BSH (runs are sorted by bin)
     {
       // CS_BMAX / CS_BLOCK consecutive buckets per thread: one binary search for the
@@ -362,8 +389,12 @@ __device__ bool cos_body(const CsrView& v, const CosParams& P, const CosState& S
       }
       __builtin_amdgcn_wave_barrier();
     }
-    if (unsorted) {  // B.B = sum_q I_q * (sum of I over the member's peaks in q's bin)
-      bb = 0.0;
+    // the O(m^2) pass (whole wave): this lane's share of
+    // B.B = sum_q I_q * (sum of I over the member's peaks in q's bin, in input order);
+    // returns whether one of those bin sums is +-inf
+    auto dense_bb = [&](double& out) -> bool {
+      bool binf = false;
+      out = 0.0;
       for (int ch = 0; ch < m; ch += kWave) {
         const int q = ch + lane;
         const double I = q < m ? v.inten[a + q] : 0.0;
@@ -378,14 +409,35 @@ __device__ bool cos_body(const CsrView& v, const CosParams& P, const CosState& S
             if (bm >= 0 && L.wk[wid][t] == (int32_t)bm) sb += L.wI[wid][t];
           __builtin_amdgcn_wave_barrier();
         }
-        if (bm >= 0) bb += I * sb;
+        if (bm >= 0) {
+          out += I * sb;
+          binf |= fabs(sb) == inf;
+        }
       }
+      return __ballot(binf) != 0ull;
+    };
+    bool b_inf = false;  // a bin of the member sums to +-inf (looked for only where it matters)
+    if (unsorted) {
+      b_inf = dense_bb(bb);
     } else if (carry_b >= 0 && lane == 0) {
       bb += carry_s * carry_s;
     }
     ab = wave_sum_f64(ab);
     bb = wave_sum_f64(bb);
-    if (lane == 0) cos_out[s0 + j] = (aa == 0.0 || bb == 0.0) ? 0.0 : ab / sqrt(aa * bb);
+    double res = (aa == 0.0 || bb == 0.0) ? 0.0 : ab / sqrt(aa * bb);
+    // np.dot over the dense vectors meets a bin that sums to +-inf with the other side's
+    // 0.0 (inf * 0 = nan) or with a finite value (inf / sqrt(inf) = nan): NaN either way,
+    // which the sparse sums alone miss.  Such a bin makes its own norm non-finite, so only
+    // then are the two sides searched for one (a finite square that overflows is none).
+    if (!(fabs(aa * bb) < inf) && aa != 0.0 && bb != 0.0) {  // (uniform: every lane holds the sums)
+      bool any_inf = L.inf_lo < ic || (has_extra && fabs(A_kc) == inf) || b_inf;
+      if (!any_inf && !unsorted) {
+        double unused;
+        any_inf = dense_bb(unused);
+      }
+      if (any_inf) res = nan;
+    }
+    if (lane == 0) cos_out[s0 + j] = res;
   }
   __syncthreads();
   if (tid == 0) {  // average_cos_dist: sequential sum in member order (benchmark.py:33-36)

@@ -8,6 +8,7 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
+import binned_cosine_cases as cases
 from conftest import load_golden
 from oracle import np_oracle
 from specpride_amd import benchmark, engine
@@ -133,3 +134,106 @@ def test_binned_cosine_representatives_past_lds(gpu):
     got = _run(csr, rep_off, rep_mz, rep_int)
     assert np.all(got[2][:csr.n_clusters] == 0)
     _check(got, np_oracle.binned_cosine(csr, rep_off, rep_mz, rep_int), csr.n_clusters, csr.n_spectra)
+
+
+# ---- the branches ordinary spectra never take (tests/binned_cosine_cases.py), against the
+# reference's own results on them (tests/golden/binned_cosine_edges.npz)
+@pytest.fixture(scope="module")
+def edge_golden():
+    import os
+
+    from conftest import GOLDEN
+
+    return np.load(os.path.join(GOLDEN, "binned_cosine_edges.npz"))
+
+
+def _run_case(z, name):
+    csr, rep_off, rep_mz, rep_int, s, want = cases.golden_case(z, name)
+    got = _run(csr, rep_off, rep_mz, rep_int, s)
+    _check(got, want, csr.n_clusters, csr.n_spectra)
+    return got, want, csr
+
+
+def test_binned_cosine_rep_on_edge(gpu, edge_golden):
+    """Representative peaks on the rightmost edge of the pair's cut: shifted into the last
+    bin (with and without a run of that bin, sorted or not, below and past the bucket
+    table), and ordinary bins against a member that ends higher."""
+    _run_case(edge_golden, "rep_on_edge")
+
+
+def test_binned_cosine_high_mz(gpu, edge_golden):
+    """Bins on both sides of 524,288, the end of the bucket table (m/z ~2,622.77), up to
+    m/z 4,500: the binary-search tail of the run lookup, in both kernels."""
+    _run_case(edge_golden, "high_mz")
+
+
+def test_binned_cosine_chunk_runs(gpu, edge_golden):
+    """Runs of one bin longer than a chunk, ending exactly at a chunk's last peak,
+    filling a chunk, and closing a member of 64, 65 or 128 peaks."""
+    _run_case(edge_golden, "chunk_runs")
+
+
+def test_binned_cosine_sandwiched(gpu, edge_golden):
+    """An invalid peak (above the cut, below the first edge, NaN) between two peaks of
+    one bin, inside a chunk and across a chunk boundary: one sum, not two."""
+    _run_case(edge_golden, "sandwiched")
+
+
+def test_binned_cosine_many_deferred(gpu, edge_golden):
+    """More deferred clusters than the global-scratch kernel has workgroups: every slice
+    serves a second, shorter representative.  Twice on one DeviceBatch (the workspace is
+    reused): the same bits."""
+    csr, rep_off, rep_mz, rep_int, s, want = cases.golden_case(edge_golden, "many_deferred")
+    assert int((np.diff(rep_off) > cases.RCAP).sum()) > cases.FALLBACK_BLOCKS
+    b = engine.DeviceBatch.from_host(csr)
+    dev = [_dev(rep_off), _dev(rep_mz), _dev(rep_int)]
+    first = engine.binned_cosine(b, *dev, mz_space=s).to_host()
+    second = engine.binned_cosine(b, *dev, mz_space=s).to_host()
+    _check(first, want, csr.n_clusters, csr.n_spectra)
+    _check(second, want, csr.n_clusters, csr.n_spectra)
+    for x, y in zip(first, second):
+        np.testing.assert_array_equal(x, y)
+
+
+def test_binned_cosine_rcap_boundary(gpu, edge_golden):
+    """One cluster with the first 511, 512 and 513 peaks of one representative: the last
+    lengths of the LDS kernel and the first of the global-scratch kernel."""
+    got, want, csr = _run_case(edge_golden, "rcap_boundary")
+    n = csr.n_spectra // 3
+    cos, wcos = got[0][:csr.n_spectra].reshape(3, n), want[0].reshape(3, n)
+    for i, j in ((0, 1), (1, 2), (0, 2)):
+        same = wcos[i] == wcos[j]
+        np.testing.assert_array_equal(cos[i][same], cos[j][same])
+        if want[1][i] == want[1][j]:
+            assert got[1][i] == got[1][j]
+
+
+@pytest.mark.parametrize("s", cases.SPACINGS)
+def test_binned_cosine_mz_space(gpu, edge_golden, s):
+    """Other bin widths: the edges, and the decimals of the on-edge rounding (8, 7, 7, 6),
+    with an on-edge member and an on-edge representative built for each."""
+    _run_case(edge_golden, f"mz_space_{s}")
+
+
+def test_binned_cosine_nonfinite(gpu, edge_golden):
+    """Infinite and NaN intensities as the reference's dense dot products treat them: an
+    infinite bin inside the cut gives NaN unless the partner is all zero (0.0), past the
+    cut it is dropped, and a finite square that overflows gives 0.0."""
+    _run_case(edge_golden, "nonfinite")
+
+
+def test_binned_cosine_unresolved_past_max_rep_peaks(gpu, edge_golden):
+    """A representative longer than the caller's max_rep_peaks is reported unresolved
+    (include/specpride.h); every other cluster of the call is scored."""
+    csr, rep_off, rep_mz, rep_int, s, want = cases.golden_case(edge_golden, "unresolved")
+    lens = np.diff(rep_off)
+    b = engine.DeviceBatch.from_host(csr)
+    cos, avg, st = engine.binned_cosine(b, _dev(rep_off), _dev(rep_mz), _dev(rep_int), mz_space=s,
+                                        max_rep_peaks=cases.UNRESOLVED_MAX_REP).to_host()
+    long = lens > cases.UNRESOLVED_MAX_REP
+    assert long.sum() == 1 and (lens[~long] > cases.RCAP).sum() == 2
+    assert np.all(st[:csr.n_clusters][long] == engine.STATUS_UNRESOLVED)
+    keep = ~np.repeat(long, np.diff(csr.cluster_off))
+    np.testing.assert_array_equal(st[:csr.n_clusters][~long], want[2][~long])
+    np.testing.assert_allclose(cos[:csr.n_spectra][keep], want[0][keep], rtol=RTOL, atol=0, equal_nan=True)
+    np.testing.assert_allclose(avg[:csr.n_clusters][~long], want[1][~long], rtol=RTOL, atol=0, equal_nan=True)
