@@ -25,7 +25,7 @@
 // a lifetime that issues no global load of its own -- the workgroup's last wave claims
 // the next cluster and fetches its header (offsets, charges, precursors: RegHeader,
 // bin_mean.hip) into the other of two LDS buffers -- the claim during the medoid's rows,
-// the dependent loads beside the two waves that compute the medoid's tail -- so the next
+// the dependent loads beside the waves that finish the medoid's tail -- so the next
 // set-up reads LDS and waits for no round trip (FusedPrefetch).
 #include "bin_mean.hip"
 #include "medoid.hip"
@@ -47,8 +47,9 @@ static_assert(BM_BLOCK == MD_BLOCK, "one workgroup shape for both bodies");
 
 // The next cluster's header, fetched by ONE wave (all 64 lanes active) in four steps at
 // wave-uniform program points: the claim goes out a phase ahead (the medoid's rows), the
-// other three run back to back in the medoid's tail, where this wave has no other work and
-// waits for each step's loads itself:
+// other three run back to back in the medoid's tail -- at once in a cluster of up to 32
+// spectra, where this wave has no other work, and after its Gram tile past 32 -- and the
+// wave waits for each step's loads itself:
 //   claim    the queue head's atomicAdd                       -> tc
 //   offsets  tc -> H->c; cluster_off[c], cluster_off[c + 1]   -> toff
 //   spectra  toff -> H->s0, H->n; spec_off, charge, prec_mz   -> tso, tz, tp
@@ -199,10 +200,14 @@ __device__ __forceinline__ bool medoid_from_codes(int64_t* rep, double* totals_o
     }
   });
   SPX_STAMP2(-1, 5);
-  // the tail's work is waves 0 and 1's (n <= 50 here): the prefetching wave runs the
-  // remaining steps on its own beside them, waiting for each step's loads (Hn lies outside
-  // the medoid's LDS, and the loop-top barrier publishes it)
-  medoid_tail<MD_BLOCK, MR_UMAX, MD_KWMAX>(L, n, KW, s0, c, rep, totals_out, [&]() __attribute__((always_inline)) {
+  // up to 32 spectra the tail's work is wave 0's: the prefetching wave runs the remaining
+  // steps on its own beside it, back to back, waiting for each step's loads.  Past 32 it has
+  // a Gram tile of its own first and runs the steps behind the tail's hand-off barrier,
+  // beside the two finishing waves (medoid_tail_regs calls the hook there) --
+  // before the tail's last barrier in every case (Hn lies outside the medoid's LDS, and
+  // the loop-top barrier publishes it)
+  medoid_tail<MD_BLOCK, MR_UMAX, MD_KWMAX>(L, n, KW, s0, c, rep, totals_out,
+                                           [&]() __attribute__((always_inline)) {
     if (!fused_prefetch_wave()) return;
     pf.offsets(v, Hn);
     pf.spectra(v, Hn);

@@ -16,6 +16,7 @@
 // overflow) go to a deferred list and through the grid-parallel passes and the
 // MFMA Gram kernel below, with state in a bump-allocated global arena.
 #pragma once
+#include <cstddef>
 #include <type_traits>
 
 #include "spx_device.hpp"
@@ -39,6 +40,13 @@ constexpr int MD_NMAX = 64;
 #endif
 #ifndef SPX_MD_MFMA_NMIN
 #define SPX_MD_MFMA_NMIN 1  // the register tail for clusters of more spectra than this (1: all)
+#endif
+// The register tail's variants (0: the code before them; A/B handles):
+#ifndef SPX_MD_P4_WAVES
+#define SPX_MD_P4_WAVES 1  // past 32 spectra: one Gram tile per wave on four waves, not two on two
+#endif
+#ifndef SPX_MD_DIAG
+#define SPX_MD_DIAG 1      // a diagonal tile converts one operand fragment for both MFMA operands
 #endif
 constexpr int MD_KWMAX = SPX_MD_KWMAX;  // row words (odd stride): <= 64 * MD_KWMAX occupied bins per small cluster
 
@@ -221,6 +229,13 @@ struct MedoidRegSmem {
       unsigned long long sbits[UMAX * BLOCK / 64];  // bit r: peak r starts spectrum >= 1 (ends a spectrum)
       uint8_t spre[UMAX * BLOCK / 64];              // spectra started (ended) before word w
     } a;                                         // P0..P4a
+    // P4 of the 256-thread kernels past 32 spectra: what the row-tile-0 wave of a column
+    // tile hands to its row-tile-1 wave (medoid_tail_regs).  Over a.bits / a.pre, which P3
+    // is the last to read; the rows behind them stay live.
+    struct {
+      double acc[2][4][kWave];                   // [column tile][accumulator i][lane]
+      double cs0[32];                            // column tile 0: the finished column sums
+    } h;
     double d[MR_TRI];                            // P4b..P5: d(i, j), j >= i, row-major packed
     struct {
       double d[MR_TRI];
@@ -245,7 +260,7 @@ struct MedoidNoHook {
 
 // P4..P6 in registers, one wave per 32 columns (wave 0: spectra 0..31, wave 1: 32..63),
 // for the 256-thread kernels.  The wave computes the full 32 x 32 Gram tile of its columns
-// against each 32-row tile -- one v_mfma_scale_f32_32x32x64_f8f6f4 per 64-bin row word, FP4
+// against a 32-row tile -- one v_mfma_scale_f32_32x32x64_f8f6f4 per 64-bin row word, FP4
 // 0/1 operands at unit scale, so the f32 sums are the integer counts |B_r ∩ B_j| -- and
 // folds the tile into the totals straight from the accumulator.  The C/D layout gives lane
 // (j = lane & 31, fh = lane >> 5) column j at rows (q & 3) + 8 * (q >> 2) + 4 * fh: of every
@@ -256,19 +271,44 @@ struct MedoidNoHook {
 // both are summed at once, the other side's terms replaced by +0.0 (every partial sum is
 // >= +0.0, so adding it changes nothing).  Nothing is written to LDS before the result:
 // the rows stay in place, the distances never exist all at once.
-template <int BLOCK, int UMAX, int KWMAX>
+//
+// Past 32 spectra there are four tiles (column tile ct, row tile t) and each of the four
+// waves takes one: wave w has ct = w & 1; waves 2 and 3 take row tile 0, waves 0 and 1 row
+// tile 1.  Every accumulator chain adds row tile 0's groups first, so the row-tile-0 wave
+// folds its tile and hands its partial sums through LDS (L.u.h) to the row-tile-1 wave of
+// its column tile, which goes on with the same chains from its own accumulator and finishes
+// as before: the combine, the sequential tail rows, the division, its half of the argmin.
+// What crosses, per lane (the +0.0 rule again):
+//   ct = 0  rows 32..63 lie below every column 0..31's diagonal: they add to the row sums
+//           only.  The four row-sum accumulators cross; the column sum is complete after
+//           row tile 0, so its wave combines it and hands over the one finished value.
+//   ct = 1  rows 0..31 lie above every column 32..63's diagonal: they add to the column
+//           sums only.  The four column-sum accumulators cross; the row sums start at +0.0.
+// One barrier more per cluster (the hand-off; the other joins the two argmin halves).
+// hook(): the fused pass's prefetch steps (offsets, spectra, commit); every wave calls it
+// and only the prefetching wave (wave 3, a row-tile-0 wave) acts.  It is called at ONE
+// program point, behind the hand-off barrier: up to 32 spectra that wave has no tile and
+// reaches it at once; past 32 it reaches it after its tile, and its three round trips run
+// beside the finishing waves' fold, tail rows and argmin.  (One call site on purpose: with
+// more the fused kernel spills in its bin-mean phases)
+template <int BLOCK, int UMAX, int KWMAX, class Hook>
 __device__ __forceinline__ void medoid_tail_regs(MedoidRegSmem<BLOCK, UMAX, KWMAX>& L, int n, int KW, int64_t s0,
-                                                 int64_t c, int64_t* rep, double* totals_out) {
-  const int lane = lane_id(), wid = wave_id();
+                                                 int64_t c, int64_t* rep, double* totals_out, const Hook& hook) {
+  static_assert(sizeof(L.u.h) <= offsetof(decltype(L.u.a), rows), "the hand-off lies in front of the rows");
+  const int lane = lane_id(), wid = __builtin_amdgcn_readfirstlane(wave_id());
   const int fr = lane & 31, fh = lane >> 5;
-  const bool two = n > 32;  // uniform: two column waves, two row tiles each
+  const bool two = n > 32;                     // uniform: two column tiles, two row tiles
+  const bool split = SPX_MD_P4_WAVES && two;   // uniform: one tile per wave
   double best = __longlong_as_double(0x7ff0000000000000ll);
   int idx = 0x7fffffff;
-  if (wid == 0 || (two && wid == 1)) {  // wave-uniform
-    const int j = wid * 32 + fr;        // this lane's column (both halves of the wave)
+  const bool works = split || wid == 0 || (two && wid == 1);  // wave-uniform
+  {
+    const int ct = wid & 1;
+    const int j = ct * 32 + fr;         // this lane's column (both halves of the wave)
     const bool jv = j < n;
-    const int pj = L.soff[j + 1] - L.soff[j];  // (j <= 63: inside soff and totals for every lane)
-    const double rj = L.totals[j];
+    // (j <= 63: inside soff and totals for every lane; a wave without tile work reads nothing)
+    const int pj = works ? L.soff[j + 1] - L.soff[j] : 0;
+    const double rj = works ? L.totals[j] : 0.0;
     const unsigned long long* pb = L.u.a.rows + (jv ? j : 0) * KW;
     const unsigned long long mb = jv ? ~0ull : 0ull;
     // numpy's leaf sum: 8 strided accumulators over the indices below lim, then a sequential tail
@@ -276,23 +316,39 @@ __device__ __forceinline__ void medoid_tail_regs(MedoidRegSmem<BLOCK, UMAX, KWMA
     double ra[4], ca[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) ra[i] = ca[i] = 0.0;
+    double cs_done = 0.0;  // ct = 0 past the hand-off: the column sum as row tile 0 finished it
     md_f32x16 acc;
-    const int ntile = two ? 2 : 1;
-    for (int t = 0; t < ntile; ++t) {  // uniform: row tile 0, then 1 -- each r[k] chain in index order
+    // the Gram tile of this wave's columns against row tile t, into acc
+    auto gram = [&](int t) __attribute__((always_inline)) {
       const int ia = t * 32 + fr;
       const unsigned long long* pa = L.u.a.rows + (ia < n ? ia : 0) * KW;
       const unsigned long long ma = ia < n ? ~0ull : 0ull;
 #pragma unroll
       for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
-      unsigned long long wa = pa[0] & ma, wb = pb[0] & mb;  // one word ahead
-      for (int w = 0; w < KW; ++w) {
-        const int wn = w + 1 < KW ? w + 1 : w;
-        const unsigned long long na = pa[wn] & ma, nb = pb[wn] & mb;
-        acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(md_frag4(wa, fh), md_frag4(wb, fh), acc, 4, 4, 0, 0,
-                                                              0, 0);
-        wa = na;
-        wb = nb;
+      if (SPX_MD_DIAG && t == ct) {
+        // a diagonal tile: the rows are the columns (pa == pb), one fragment serves both operands
+        unsigned long long wa = pa[0] & ma;  // one word ahead
+        for (int w = 0; w < KW; ++w) {
+          const int wn = w + 1 < KW ? w + 1 : w;
+          const unsigned long long na = pa[wn] & ma;
+          const md_i32x8 f = md_frag4(wa, fh);
+          acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(f, f, acc, 4, 4, 0, 0, 0, 0);
+          wa = na;
+        }
+      } else {
+        unsigned long long wa = pa[0] & ma, wb = pb[0] & mb;  // one word ahead
+        for (int w = 0; w < KW; ++w) {
+          const int wn = w + 1 < KW ? w + 1 : w;
+          const unsigned long long na = pa[wn] & ma, nb = pb[wn] & mb;
+          acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(md_frag4(wa, fh), md_frag4(wb, fh), acc, 4, 4, 0,
+                                                                0, 0, 0);
+          wa = na;
+          wb = nb;
+        }
       }
+    };
+    // row tile t's groups of eight rows below lim, from acc into the strided accumulators
+    auto fold = [&](int t) __attribute__((always_inline)) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int r0 = t * 32 + 8 * g;
@@ -312,60 +368,103 @@ __device__ __forceinline__ void medoid_tail_regs(MedoidRegSmem<BLOCK, UMAX, KWMA
           }
         }
       }
-    }
-    SPX_STAMP2(5, 6);
-    // fh = 0 holds (r0+r1)+(r2+r3), fh = 1 (r4+r5)+(r6+r7): one exchange, one add (the same
-    // bits in both halves: the addition commutes)
-    double rs = (ra[0] + ra[1]) + (ra[2] + ra[3]);
-    double cs = (ca[0] + ca[1]) + (ca[2] + ca[3]);
-    rs = rs + __shfl_xor(rs, 32, kWave);
-    cs = cs + __shfl_xor(cs, 32, kWave);
-    if (lim < n) {  // uniform
-      // the sequential tail, rows lim..n-1: they are the group at lim of the LAST tile (still
-      // in acc); indices lim..lim+3 sit in the fh = 0 lane and lim+4.. in fh = 1, so the sum
-      // runs on in fh = 0, is handed over once and finishes in fh = 1.  n < 8 is all tail.
-      const int gt = (lim & 31) >> 3;
-      float v[4];
+    };
+    const int t = split ? (wid >> 1) ^ 1 : 0;  // this wave's one tile past 32 spectra
+    if (works) {
+      if (split) {
+        gram(t);
+        if (t == 0) {
+          fold(0);
+          // hand over: the accumulators row tile 1 goes on with, and (ct = 0) the finished column sum
 #pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = acc[i];
-#pragma unroll
-      for (int g = 1; g < 4; ++g) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = g == gt ? acc[4 * g + i] : v[i];
+          for (int i = 0; i < 4; ++i) L.u.h.acc[ct][i][lane] = ct == 0 ? ra[i] : ca[i];
+          if (ct == 0) {
+            double cs = (ca[0] + ca[1]) + (ca[2] + ca[3]);
+            cs = cs + __shfl_xor(cs, 32, kWave);
+            if (fh == 0) L.u.h.cs0[fr] = cs;
+          }
+        }
+      } else {
+        const int ntile = !SPX_MD_P4_WAVES && two ? 2 : 1;
+        for (int tt = 0; tt < ntile; ++tt) {  // uniform: row tile 0, then 1 -- each r[k] chain in index order
+          gram(tt);
+          fold(tt);
+        }
       }
-      const int rb = lim + 4 * fh;  // rb + 4 <= 64: lim <= 56 here
-      int so[5];
-#pragma unroll
-      for (int i = 0; i < 5; ++i) so[i] = L.soff[rb + i];
-      double tr[4], tc[4];
+    }
+    // the hand-off: the row-tile-0 waves have folded their groups, the row-tile-1 waves
+    // hold their tiles in acc
+    if (split) lds_barrier();  // every wave
+    // the prefetch steps, at the one point every cluster's prefetching wave passes: at once
+    // up to 32 spectra (it has no tile), behind its tile and the hand-off past 32 -- beside the
+    // finishing waves either way
+    hook();
+    if (works && wid < 2 && split) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int r = rb + i;
-        const double d = md_dist_rd((double)v[i], so[i + 1] - so[i], L.totals[r], pj, rj);
-        tr[i] = (r < n && r >= j) ? d : 0.0;
-        tc[i] = (r < n && r <= j) ? d : 0.0;
+        const double h = L.u.h.acc[ct][i][lane];
+        ra[i] = ct == 0 ? h : 0.0;
+        ca[i] = ct == 0 ? 0.0 : h;
       }
-      const double rs0 = (((rs + tr[0]) + tr[1]) + tr[2]) + tr[3];  // fh = 0: indices lim..lim+3
-      const double cs0 = (((cs + tc[0]) + tc[1]) + tc[2]) + tc[3];
-      const double rsh = __shfl_xor(rs0, 32, kWave), csh = __shfl_xor(cs0, 32, kWave);
-      rs = (((rsh + tr[0]) + tr[1]) + tr[2]) + tr[3];  // fh = 1: indices lim+4..lim+7
-      cs = (((csh + tc[0]) + tc[1]) + tc[2]) + tc[3];
+      cs_done = L.u.h.cs0[fr];
+      fold(1);
     }
-    // the fh = 1 lanes hold the finished sums of their columns
-    const double row = 0.0 + rs, col = 0.0 + cs;
-    const double tot = (row + col) / (double)n;  // (row + col) / n
-    if (fh == 1 && jv) {
-      if (totals_out) totals_out[s0 + j] = tot;
-      best = tot;
-      idx = j;
+    if (works && wid < 2) {  // wave-uniform: the waves that hold the last row tile finish their columns
+      SPX_STAMP2(5, 6);
+      // fh = 0 holds (r0+r1)+(r2+r3), fh = 1 (r4+r5)+(r6+r7): one exchange, one add (the same
+      // bits in both halves: the addition commutes)
+      double rs = (ra[0] + ra[1]) + (ra[2] + ra[3]);
+      double cs = (ca[0] + ca[1]) + (ca[2] + ca[3]);
+      rs = rs + __shfl_xor(rs, 32, kWave);
+      cs = cs + __shfl_xor(cs, 32, kWave);
+      if (split && ct == 0) cs = cs_done;  // (row tile 1 added +0.0 only)
+      if (lim < n) {  // uniform
+        // the sequential tail, rows lim..n-1: they are the group at lim of the LAST tile (still
+        // in acc); indices lim..lim+3 sit in the fh = 0 lane and lim+4.. in fh = 1, so the sum
+        // runs on in fh = 0, is handed over once and finishes in fh = 1.  n < 8 is all tail.
+        const int gt = (lim & 31) >> 3;
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = acc[i];
+#pragma unroll
+        for (int g = 1; g < 4; ++g) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) v[i] = g == gt ? acc[4 * g + i] : v[i];
+        }
+        const int rb = lim + 4 * fh;  // rb + 4 <= 64: lim <= 56 here
+        int so[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) so[i] = L.soff[rb + i];
+        double tr[4], tc[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int r = rb + i;
+          const double d = md_dist_rd((double)v[i], so[i + 1] - so[i], L.totals[r], pj, rj);
+          tr[i] = (r < n && r >= j) ? d : 0.0;
+          tc[i] = (r < n && r <= j) ? d : 0.0;
+        }
+        const double rs0 = (((rs + tr[0]) + tr[1]) + tr[2]) + tr[3];  // fh = 0: indices lim..lim+3
+        const double cs0 = (((cs + tc[0]) + tc[1]) + tc[2]) + tc[3];
+        const double rsh = __shfl_xor(rs0, 32, kWave), csh = __shfl_xor(cs0, 32, kWave);
+        rs = (((rsh + tr[0]) + tr[1]) + tr[2]) + tr[3];  // fh = 1: indices lim+4..lim+7
+        cs = (((csh + tc[0]) + tc[1]) + tc[2]) + tc[3];
+      }
+      // the fh = 1 lanes hold the finished sums of their columns
+      const double row = 0.0 + rs, col = 0.0 + cs;
+      const double tot = (row + col) / (double)n;  // (row + col) / n
+      if (fh == 1 && jv) {
+        if (totals_out) totals_out[s0 + j] = tot;
+        best = tot;
+        idx = j;
+      }
+      // P6: lowest index of the minimum over the wave's columns
+      SPX_STAMP2(6, -1);
+      // (the wave's minimum by DPP, then the first lane that holds it: lanes 32..63 carry
+      // columns in ascending order, the others +inf, and a total is never NaN)
+      const double least = wave_min_dpp(best);
+      idx = wid * 32 + (__ffsll((unsigned long long)__ballot(best == least)) - 1 - 32);
+      best = least;
     }
-    // P6: lowest index of the minimum over the wave's columns
-    SPX_STAMP2(6, -1);
-    // (the wave's minimum by DPP, then the first lane that holds it: lanes 32..63 carry
-    // columns in ascending order, the others +inf, and a total is never NaN)
-    const double least = wave_min_dpp(best);
-    idx = wid * 32 + (__ffsll((unsigned long long)__ballot(best == least)) - 1 - 32);
-    best = least;
   }
   if (two) {  // uniform: wave 1's minimum joins wave 0's (every index of wave 1 is the higher one)
     if (wid == 1 && lane == 0) {
@@ -382,9 +481,10 @@ __device__ __forceinline__ void medoid_tail_regs(MedoidRegSmem<BLOCK, UMAX, KWMA
   SPX_STAMP2(7, 7);
 }
 
-// hook() runs right after the barrier that opens P4 (every wave calls it, no barrier inside):
+// hook() runs once after the barrier that opens P4 (every wave calls it, no barrier inside):
 // the fused pass's persistent loop lets its prefetching wave fetch the next cluster's header
-// there, beside the waves that compute.
+// there, beside the waves that compute -- right after that barrier, or past 32 spectra behind
+// that wave's own Gram tile and the hand-off barrier (medoid_tail_regs).
 template <int BLOCK, int UMAX, int KWMAX, class Hook = MedoidNoHook>
 __device__ __forceinline__ void medoid_tail(MedoidRegSmem<BLOCK, UMAX, KWMAX>& L, int n, int KW, int64_t s0,
                                             int64_t c, int64_t* rep, double* totals_out,
@@ -400,13 +500,13 @@ __device__ __forceinline__ void medoid_tail(MedoidRegSmem<BLOCK, UMAX, KWMAX>& L
   }
   __syncthreads();
   SPX_STAMP2(4, -1);
-  if constexpr (!std::is_same<Hook, MedoidNoHook>::value) hook();
   if constexpr (BLOCK == MD_BLOCK) {
     if (SPX_MD_MFMA_NMIN <= 1 || n > SPX_MD_MFMA_NMIN) {  // uniform
-      medoid_tail_regs<BLOCK, UMAX, KWMAX>(L, n, KW, s0, c, rep, totals_out);
+      medoid_tail_regs<BLOCK, UMAX, KWMAX>(L, n, KW, s0, c, rep, totals_out, hook);
       return;
     }
   }
+  hook();
 
   auto row_start = [&](int i) { return i * n - (i * (i - 1)) / 2; };
   // The LDS tail: the wide kernel (up to 95 row words, 128 VGPRs) keeps the AND + popcount
